@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- Reflow memoization hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the set, runs the
+all-host plan that calibrates the planner's host feed rate, makes the hybrid
+plan, warms up, times the K steps and prints one compact JSON line.
+--dump-outputs DIR then writes what the last timed step returned -- every
+file's 32-byte File ID in file order, one row of 32 byte values as float32 --
+to DIR/file_ids.npy (DIR/file_ids_rank<r>.npy with N > 1 ranks); the set is
+seeded, so two builds can be compared output for output.  --full adds every
+secondary section below to the run and to the line.
 
 Primary line (value): SHA-256 digest GB/s of configs[1], the 64 GiB
 FASTQ/BAM-like skewed Fileset (4 KiB-2 GiB files), HBM-resident, per GPU.
@@ -13,7 +22,9 @@ the global Fileset is N configs[1]-distributed sets (seeds 0x5EED0004+g),
 sharded LPT by size over the ranks (weak scaling: 64 GiB per GPU; N = 8 is
 configs[3]'s 512 GiB).
 
-Secondary, in the same JSON line:
+Secondary, in the same JSON line ("roofline", "host_leg" and "composition"
+come from the timed steps themselves and are always there; the rest take runs
+of their own and need --full):
   "roofline"          the dominant GPU kernel of the hybrid run vs the
                       skew-aware floor; "roofline_gpu_only": k1_sha256_duo on
                       the GPU-only plan (one run); "host_leg": the SHA-NI leg
@@ -1605,6 +1616,35 @@ def parity_summary(sha, c1, dag, dag100, probe, cpu):
     return {"all": bool(ran) and all(ran), "checks_run": len(ran), **checks}
 
 
+# What --full adds to a plain run: the --skip names of the secondary sections,
+# and the line's keys that only they (or the GPU-only plan, or the measured
+# VALU ceiling) fill in
+FULL_SECTIONS = ("lower", "c1", "install", "dag", "dag100m", "piece", "persample", "checkpoint", "probe", "cpu")
+FULL_KEYS = ("gpu_only_gbps", "incremental_mnodes_per_s", "incremental_100m_mnodes_per_s", "valu_measured_tops",
+             "parity", "roofline_gpu_legs", "roofline_gpu_only", "gpu_only", "cpu_baseline", "c1", "incremental",
+             "incremental_100m", "lowering", "probe", "budget")
+
+
+def dump_outputs(path, dist, sha):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step -- this rank's File IDs (the 32-byte SHA-256 digest of every file,
+    in file order), one row of 32 byte values per file as float32 (exact)."""
+    os.makedirs(path, exist_ok=True)
+    name = "file_ids" if dist.world == 1 else "file_ids_rank%d" % dist.rank
+    np.save(os.path.join(path, name + ".npy"), sha["_digests"].astype(np.float32))
+
+
+def write_all(fd, data):
+    """os.write until every byte is out: one call may write only part of a
+    long line, and a full non-blocking pipe refuses it until it is drained."""
+    import select
+    while data:
+        try:
+            data = data[os.write(fd, data):]
+        except BlockingIOError:
+            select.select([], [fd], [])
+
+
 def main():
     # stdout carries exactly ONE line, the JSON result: everything else any
     # library prints on the C-level stdout (gloo's "[Gloo] Rank r is
@@ -1632,10 +1672,17 @@ def main():
     ap.add_argument("--cpu-sample-gib", type=float, default=16.0)
     ap.add_argument("--gpu-only-run", type=int, default=1, help="one GPU-only run (duo roofline)")
     ap.add_argument("--budget-s", type=float, default=420.0)
-    ap.add_argument("--skip", default="",
-                    help="comma list of: lower,c1,install,dag,dag100m,piece,persample,checkpoint,probe,cpu")
+    ap.add_argument("--skip", default="", help="with --full, a comma list of: " + ",".join(FULL_SECTIONS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary section (GPU-only plan, c1, the DAG legs, lowering, probe, "
+                         "the CPU baselines, the measured VALU ceiling) and report them in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's File IDs to DIR/file_ids.npy (float32, one row per file)")
     args = ap.parse_args()
     args.skip = set(filter(None, args.skip.split(",")))
+    if not args.full:  # a plain run: the timed steps and what they need, nothing else
+        args.skip |= set(FULL_SECTIONS)
+        args.gpu_only_run = 0
     budget = Budget(args.budget_s)
 
     dist = Dist(args.gpus)
@@ -1681,6 +1728,8 @@ def main():
                 rccl = True
 
     sha = bench_sha(args, dist, ctx, budget)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dist, sha)
     sha_ranks = None
     if dist.world > 1:  # per rank: host-leg threads and bytes, GPU-leg bytes, step ms (is the curve host-bound?)
         hl, comp = sha["host_leg"] or {}, sha["composition"]
@@ -1729,7 +1778,7 @@ def main():
         dag_res.pop("_cpu", None)
     sha["_arena"].free()
     parity = parity_summary(sha, c1, dag_res, dag100, probe, cpu)
-    valu_tops = valu_ceiling() if dist.rank == 0 else None
+    valu_tops = valu_ceiling() if args.full and dist.rank == 0 else None
 
     if dist.rank == 0:
         workload = sha["workload"]
@@ -1778,9 +1827,12 @@ def main():
                        "elapsed_s": round(time.perf_counter() - T_START, 1)},
         }
         with_measured_valu(line, valu_tops)
+        if not args.full:  # the sections that did not run would only be nulls
+            line = {k: v for k, v in line.items() if k not in FULL_KEYS}
+        line["full"] = bool(args.full)
         line["summary"] = run_summary(line)  # last: the driver's record keeps the line's tail
         sys.stdout.flush()
-        os.write(result_fd, (json.dumps(line) + "\n").encode())
+        write_all(result_fd, (json.dumps(line) + "\n").encode())
     if comm is not None:
         comm.close()
     ctx.close()

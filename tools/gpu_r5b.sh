@@ -45,7 +45,7 @@ if has k4; then
   mkdir -p $out/k4
   for c in FETCH_SIZE WRITE_SIZE; do
     step "k4 $c" && timeout -s KILL 500 rocprofv3 --pmc $c --output-format csv -d $out/k4/$c -o p \
-        -- python3 bench.py --steps 1 --warmup 0 --skip cpu,lower,dag,dag100m,piece,persample,c1,install,checkpoint \
+        -- python3 bench.py --full --steps 1 --warmup 0 --skip cpu,lower,dag,dag100m,piece,persample,c1,install,checkpoint \
         > $out/k4/$c.json 2> $out/k4/$c.log || exit $?
   done
   python3 tools/pmc_k4_summary.py $out/k4/FETCH_SIZE/p_counter_collection.csv $out/k4/WRITE_SIZE/p_counter_collection.csv \

@@ -15,7 +15,7 @@ rocm-smi --showclocks > $out/clocks.txt 2>&1 || true
 if has trace; then
   echo "== trace ($(date +%T))"
   timeout -s KILL 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o bench \
-      -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.log || exit $?
+      -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.log || exit $?
 fi
 if has sqw || has k4; then
   w=""; has sqw && w="sqw"; has k4 && w="$w,k4"

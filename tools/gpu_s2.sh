@@ -17,7 +17,7 @@ if [ "$2" = A ]; then
     step focus && { [ -z "$FOCUS" ] || timeout -k 10 400 python -u -m pytest $FOCUS -x -v --timeout 200 --timeout-method thread > $out/focus.log 2>&1; } && tail -2 $out/focus.log &&
     step tests && timeout -k 10 700 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > $out/gpu_tests.log 2>&1 && tail -2 $out/gpu_tests.log &&
     step smoke && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 && tail -1 $out/smoke.log &&
-    step bench && RF_LOWER_TIMING=1 timeout -k 10 700 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.log &&
+    step bench && RF_LOWER_TIMING=1 timeout -k 10 700 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.log &&
     tail -4 $out/bench.log
 else
 step forms && timeout -k 10 400 python -u tools/dag_forms.py --c2 --c4-ranks 8 > $out/forms_new.json 2> $out/forms_new.log &&

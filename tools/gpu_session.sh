@@ -16,7 +16,7 @@ echo "== smoke" && \
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 && \
 tail -2 $out/smoke.log && \
 echo "== bench" && \
-timeout -k 10 700 python -u bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.log
+timeout -k 10 700 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.log
 rc=$?
 tail -3 $out/focus.log 2>/dev/null
 tail -3 $out/gpu_tests.log 2>/dev/null

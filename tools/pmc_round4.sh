@@ -26,7 +26,7 @@ if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
   mkdir -p "$OUT/bench"
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 500 rocprofv3 --pmc $c --output-format csv -d "$OUT/bench/$c" -o p \
-        -- python3 bench.py --steps 1 --warmup 0 --skip cpu,lower,dag,dag100m,piece,probe,c1 \
+        -- python3 bench.py --full --steps 1 --warmup 0 --skip cpu,lower,dag,dag100m,piece,probe,c1 \
         > "$OUT/bench/$c.json" 2> "$OUT/bench/$c.log" || { rc=$?; echo "pmc bench $c failed rc=$rc"; exit $rc; }
   done
   python3 tools/pmc_summary.py "$OUT/bench/FETCH_SIZE/p_counter_collection.csv" \
