@@ -64,6 +64,9 @@ int rf_init(int device, rf_ctx **out);
 void rf_destroy(rf_ctx *ctx);
 const char *rf_last_error(void);
 int rf_device_count(int *n);
+/* The device's compute units as the K1 planner counts them (its octo / pair /
+ * lanes thresholds are 16, 64 and 5*256 messages per CU). */
+int rf_device_cus(rf_ctx *ctx, int *n_cu);
 /* Blocks until all work queued on the context's stream finished. */
 int rf_sync(rf_ctx *ctx);
 /* Version string, e.g. "reflow-hip 0.1 gfx950". */

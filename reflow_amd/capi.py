@@ -25,7 +25,7 @@ RF_SHA_NO_HOST = 64
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
-    "rf_init", "rf_destroy", "rf_last_error", "rf_device_count", "rf_sync", "rf_version",
+    "rf_init", "rf_destroy", "rf_last_error", "rf_device_count", "rf_device_cus", "rf_sync", "rf_version",
     "rf_sha256_batch", "rf_sha256_arena", "rf_sha_plan_create", "rf_sha_plan_run",
     "rf_sha_plan_stats", "rf_sha_plan_destroy", "rf_gen_fill", "rf_fileset_digest_batch",
     "rf_fileset_digest_device", "rf_install_dir", "rf_install_info", "rf_install_entries",
@@ -280,6 +280,7 @@ def lib():
         sigs = {
             "rf_init": ([i32, vp], i32), "rf_destroy": ([vp], None),
             "rf_last_error": ([], ctypes.c_char_p), "rf_device_count": ([vp], i32),
+            "rf_device_cus": ([vp, vp], i32),
             "rf_sync": ([vp], i32), "rf_version": ([], ctypes.c_char_p),
             "rf_sha256_batch": ([vp, vp, vp, u64, vp], i32),
             "rf_sha256_arena": ([vp, vp, vp, vp, u64, vp], i32),
@@ -414,6 +415,12 @@ class Context:
         t, r, e = ctypes.c_int(0), ctypes.c_double(0), ctypes.c_int(0)
         _check(lib().rf_host_info(self._h, ctypes.byref(t), ctypes.byref(r), ctypes.byref(e)))
         return t.value, r.value, bool(e.value)
+
+    def n_cu(self):
+        """rf_device_cus: the CU count the K1 planner's form thresholds scale with."""
+        n = ctypes.c_int(0)
+        _check(lib().rf_device_cus(self._h, ctypes.byref(n)))
+        return n.value
 
     def host_link(self):
         """rf_host_link: (bytes/s the planner prices the host leg's HBM feed at,
@@ -687,7 +694,10 @@ class DeviceBuffer:
         return out
 
     def zero(self):
-        _check(lib().rf_memset_d(self.ctx.handle, self._p, 0, self.nbytes))
+        self.fill(0)
+
+    def fill(self, byte):
+        _check(lib().rf_memset_d(self.ctx.handle, self._p, int(byte), self.nbytes))
 
     def free(self):
         if self._p and self._p.value:

@@ -106,6 +106,12 @@ extern "C" void rf_destroy(rf_ctx* ctx) {
     delete ctx;
 }
 
+extern "C" int rf_device_cus(rf_ctx* ctx, int* n_cu) {
+    ARG(ctx && n_cu, "null argument");
+    *n_cu = ctx->n_cu;
+    return RF_OK;
+}
+
 extern "C" int rf_sync(rf_ctx* ctx) {
     ARG(ctx, "null ctx");
     DevGuard g(ctx->device);
