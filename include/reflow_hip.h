@@ -625,6 +625,63 @@ int rf_assoc_repair(rf_assoc *a, int kind, const uint8_t *keys32, const uint64_t
                     const int32_t *which, const uint8_t *vals32, const uint8_t *key_found);
 /* Occupied slots (live + deleted keys) and table capacity. */
 int rf_assoc_stats(rf_assoc *a, uint64_t *occupied, uint64_t *capacity);
+/* Enumeration: what a shim needs to write the tier behind to DynamoDB (one
+ * dydbassoc Put per live key, assoc/dydbassoc/dydbassoc.go:40-99) and to
+ * inspect it -- the contents of the in-memory assoc's map
+ * (test/testutil/assoc.go:21-24), which assoc.Assoc (assoc/assoc.go:26-39)
+ * itself cannot list.
+ * kind >= 0: that kind; kind < 0: every kind.  live = entries with a nonzero
+ * value, deleted = occupied slots whose value is zero (assoc.Delete is Put of
+ * a zero value, assoc/assoc.go:41-44).  For kind < 0, live + deleted ==
+ * rf_assoc_stats' occupied. */
+int rf_assoc_count(rf_assoc *a, int kind, uint64_t *live, uint64_t *deleted);
+/* The live entries, each exactly once, in ascending slot order (the same
+ * arrays for an unchanged table): keys32 / vals32 rows of 32 B, kinds (int32
+ * per entry; required when kind < 0, may be NULL otherwise).  *n = the number
+ * of live entries.  If *n > cap_entries: RF_EINVAL, *n still set, and no row
+ * at index >= cap_entries is written. */
+int rf_assoc_scan(rf_assoc *a, int kind, uint64_t cap_entries, uint8_t *keys32, uint8_t *vals32,
+                  int32_t *kinds, uint64_t *n);
+/* Device-resident form on `stream`: rows below cap_entries are written, *d_n
+ * (u64) gets the number of live entries whether they fit or not (the caller
+ * compares).  A later growth or compaction waits for it before it frees the
+ * table it reads. */
+int rf_assoc_scan_device(rf_assoc *a, int kind, uint64_t cap_entries, void *d_keys32, void *d_vals32,
+                         void *d_kinds, void *d_n /* u64 */, void *stream);
+/* Rebuild the table without its deleted keys (growth carries them; the
+ * in-memory assoc drops the map entry at once, test/testutil/assoc.go:41-42):
+ * afterwards occupied == live and capacity = the smallest power of two >=
+ * max(1024, 2 * max(live, min_capacity)).  Every Get / Put / abbreviated Get
+ * behaves as before the call. */
+int rf_assoc_compact(rf_assoc *a, uint64_t min_capacity);
+/* The assoc across processes: memoization is the resume mechanism, and the
+ * assoc is where a run's cache entries outlive it (Eval.lookup reads them
+ * back, eval.go:1172-1220).
+ * save writes the live entries to `path` (beside it first, then renamed);
+ * restore checks the whole file on the host -- RF_EINVAL for a file that is
+ * not one (magic, version, flags, sizes, truncation) or whose entries break
+ * the rules below, RF_EINTEGRITY for a checksum mismatch (errors.Integrity,
+ * repository/file/repository.go:160-162); *out is then untouched -- and
+ * bulk-loads a table of capacity = the smallest power of two >=
+ * max(1024, 2 * entries).
+ * File, little-endian: header 64 B (magic "RFASSOC1", u32 version = 1, u32
+ * flags = 0, u64 n_entries, u64 chunk, 32 zero bytes); n_entries entries of
+ * 68 B (u32 kind in [0, 2^30), 32-B key, 32-B nonzero value), strictly
+ * ascending by (kind, key bytes), so equal contents give equal files; one
+ * SHA-256 per `chunk` bytes of the entry area; SHA-256(header || those
+ * digests); the end marker "RFASEND1". */
+int rf_assoc_save(rf_assoc *a, const char *path);
+int rf_assoc_restore(rf_ctx *ctx, const char *path, rf_assoc **out);
+/* The file form on the host alone (no device), as rf_bloom_format_* /
+ * rf_bloom_parse_*: chunk = checksum granule in bytes (0 = 64 MiB); the
+ * entries are given in file order.  *out_len = bytes needed (RF_EINVAL when
+ * cap is short); *n = the file's entries (RF_EINVAL with *n set when
+ * cap_entries is short).  parse applies every check of rf_assoc_restore and
+ * never reads past len. */
+int rf_assoc_file_format(const int32_t *kinds, const uint8_t *keys32, const uint8_t *vals32, uint64_t n,
+                         uint64_t chunk, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int rf_assoc_file_parse(const uint8_t *buf, uint64_t len, int32_t *kinds, uint8_t *keys32, uint8_t *vals32,
+                        uint64_t cap_entries, uint64_t *n);
 
 #ifdef __cplusplus
 }

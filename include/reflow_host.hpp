@@ -572,8 +572,24 @@ class Assoc {
     std::vector<std::pair<int, Digest>> Lookup(AssocKind kind, const std::vector<std::vector<Digest>>& node_keys,
                                                int repair, const FsidCheck& usable = nullptr,
                                                const FsidCheck& verified = nullptr);
+    // What the table holds (rf_assoc_count / rf_assoc_scan): kind < 0 = every
+    // kind.  Count = (live, deleted); Scan = the live entries, each once.
+    struct Entry {
+        int kind;
+        Digest key, value;
+    };
+    std::pair<uint64_t, uint64_t> Count(int kind = -1);
+    std::vector<Entry> Scan(int kind = -1);
+    // Rebuild without the deleted keys (rf_assoc_compact).
+    void Compact(uint64_t min_capacity = 0);
+    // The live entries as a checksummed file, and a new assoc from one
+    // (rf_assoc_save / rf_assoc_restore): the tier across processes.
+    void Save(const std::string& path);
+    static std::unique_ptr<Assoc> Restore(Engine& e, const std::string& path);
+    std::pair<uint64_t, uint64_t> Stats();  // (occupied, capacity)
 
    private:
+    Assoc() = default;
     rf_assoc* a_ = nullptr;
 };
 void Delete(Assoc& a, AssocKind kind, const Digest& k);  // assoc.go:40-43

@@ -46,6 +46,8 @@ EXPORTS = [
     "rf_dedup_digests", "rf_dedup_digests_device", "rf_assoc_lookup",
     "rf_assoc_new", "rf_assoc_destroy", "rf_assoc_put", "rf_assoc_get", "rf_assoc_get_device",
     "rf_assoc_get_abbrev", "rf_assoc_stats", "rf_assoc_put_device",
+    "rf_assoc_count", "rf_assoc_scan", "rf_assoc_scan_device", "rf_assoc_compact", "rf_assoc_save",
+    "rf_assoc_restore", "rf_assoc_file_format", "rf_assoc_file_parse",
     "rf_set_host_threads", "rf_host_info", "rf_host_rate", "rf_host_link", "rf_assoc_repair",
     "rf_sha_streams_open", "rf_sha_streams_close", "rf_sha_streams_write", "rf_sha_streams_digest",
     "rf_sha_streams_len", "rf_sha_streams_verify", "rf_sha256_verify", "rf_flow_dirty",
@@ -340,6 +342,14 @@ def lib():
             "rf_assoc_get_abbrev": ([vp, i32, vp, vp, u64, vp, vp, vp], i32),
             "rf_assoc_stats": ([vp, vp, vp], i32),
             "rf_assoc_put_device": ([vp, i32, vp, vp, vp, u64, vp], i32),
+            "rf_assoc_count": ([vp, i32, vp, vp], i32),
+            "rf_assoc_scan": ([vp, i32, u64, vp, vp, vp, vp], i32),
+            "rf_assoc_scan_device": ([vp, i32, u64, vp, vp, vp, vp, vp], i32),
+            "rf_assoc_compact": ([vp, u64], i32),
+            "rf_assoc_save": ([vp, ctypes.c_char_p], i32),
+            "rf_assoc_restore": ([vp, ctypes.c_char_p, vp], i32),
+            "rf_assoc_file_format": ([vp, vp, vp, u64, u64, vp, u64, vp], i32),
+            "rf_assoc_file_parse": ([vp, u64, vp, vp, vp, u64, vp], i32),
             "rf_set_host_threads": ([vp, i32], i32),
             "rf_sha_streams_open": ([vp, u64, u32, vp], i32), "rf_sha_streams_close": ([vp], None),
             "rf_sha_streams_write": ([vp, vp, vp, vp, u64], i32),
@@ -1155,6 +1165,48 @@ class Assoc:
         _check(lib().rf_assoc_stats(self._h, ctypes.byref(o), ctypes.byref(c)))
         return o.value, c.value
 
+    def count(self, kind=-1):
+        """rf_assoc_count: (live, deleted) of one kind, or of every kind (kind < 0)."""
+        lv, dl = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().rf_assoc_count(self._h, kind, ctypes.byref(lv), ctypes.byref(dl)))
+        return lv.value, dl.value
+
+    def scan(self, kind=-1, cap_entries=None):
+        """rf_assoc_scan: the live entries as (keys [n, 32], vals [n, 32], kinds
+        [n] int32), ascending by slot.  cap_entries: the buffers' rows (default:
+        the live count); RfError(RF_EINVAL) with .needed = n when short."""
+        cap = self.count(kind)[0] if cap_entries is None else int(cap_entries)
+        keys = np.zeros((max(cap, 1), 32), dtype=np.uint8)
+        vals = np.zeros((max(cap, 1), 32), dtype=np.uint8)
+        kinds = np.zeros(max(cap, 1), dtype=np.int32)
+        n = ctypes.c_uint64()
+        rc = lib().rf_assoc_scan(self._h, kind, cap, _ptr(keys), _ptr(vals), _ptr(kinds), ctypes.byref(n))
+        if rc != RF_OK:
+            err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+            err.needed = n.value
+            raise err
+        return keys[:n.value], vals[:n.value], kinds[:n.value]
+
+    def scan_device(self, kind, cap_entries, d_keys, d_vals, d_kinds, d_n, stream=None):
+        _check(lib().rf_assoc_scan_device(self._h, kind, cap_entries, d_keys, d_vals, d_kinds, d_n, stream))
+
+    def compact(self, min_capacity=0):
+        """rf_assoc_compact: rebuild the table without its deleted keys."""
+        _check(lib().rf_assoc_compact(self._h, min_capacity))
+
+    def save(self, path):
+        """rf_assoc_save: the live entries as a checksummed file (restore())."""
+        _check(lib().rf_assoc_save(self._h, os.fsencode(path)))
+
+    @classmethod
+    def restore(cls, ctx, path):
+        """rf_assoc_restore: a new assoc holding a saved file's entries."""
+        a = cls.__new__(cls)
+        a.ctx = ctx
+        a._h = ctypes.c_void_p()
+        _check(lib().rf_assoc_restore(ctx.handle, os.fsencode(path), ctypes.byref(a._h)))
+        return a
+
     def close(self):
         if self._h:
             lib().rf_assoc_destroy(self._h)
@@ -1165,3 +1217,32 @@ class Assoc:
             self.close()
         except Exception:
             pass
+
+
+def assoc_file_format(kinds, keys, vals, chunk=0) -> bytes:
+    """rf_assoc_file_format (host only): the assoc file of entries given in
+    (kind, key) order."""
+    kd = np.ascontiguousarray(kinds, dtype=np.int32)
+    k = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1)
+    v = np.ascontiguousarray(vals, dtype=np.uint8).reshape(-1)
+    n = len(kd)
+    need = ctypes.c_uint64()
+    lib().rf_assoc_file_format(_ptr(kd), _ptr(k), _ptr(v), n, chunk, None, 0, ctypes.byref(need))  # the size
+    out = np.zeros(need.value, dtype=np.uint8)
+    _check(lib().rf_assoc_file_format(_ptr(kd), _ptr(k), _ptr(v), n, chunk, _ptr(out), len(out), ctypes.byref(need)))
+    return out.tobytes()
+
+
+def assoc_file_parse(buf: bytes):
+    """rf_assoc_file_parse (host only): (kinds int32 [n], keys [n, 32], vals
+    [n, 32]) of an assoc file; RfError RF_EINVAL / RF_EINTEGRITY for a bad one."""
+    b = np.frombuffer(bytes(buf), dtype=np.uint8)
+    n = ctypes.c_uint64()
+    rc = lib().rf_assoc_file_parse(_ptr(b) if len(b) else None, len(b), None, None, None, 0, ctypes.byref(n))
+    if rc != RF_OK and not (rc == RF_EINVAL and n.value):
+        _check(rc)
+    kinds = np.zeros(max(n.value, 1), dtype=np.int32)
+    keys = np.zeros((max(n.value, 1), 32), dtype=np.uint8)
+    vals = np.zeros((max(n.value, 1), 32), dtype=np.uint8)
+    _check(lib().rf_assoc_file_parse(_ptr(b), len(b), _ptr(kinds), _ptr(keys), _ptr(vals), n.value, ctypes.byref(n)))
+    return kinds[:n.value], keys[:n.value], vals[:n.value]

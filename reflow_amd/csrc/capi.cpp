@@ -35,7 +35,9 @@
 #include "engine.h"
 #include "host_leg.h"
 #include "ctx.h"
+#include "assoc_io.h"
 #include "graph_internal.h"
+#include "host_par.h"
 #include "host_sha.h"
 #include "reflow_hip.h"
 #include "walk.h"
@@ -2623,10 +2625,11 @@ extern "C" int rf_dedup_digests(rf_ctx* ctx, const uint8_t* digests32, uint32_t 
 struct rf_assoc {
     rf_ctx* ctx = nullptr;
     uint32_t cap = 0;
-    // the last Get launched on a caller's stream (rf_assoc_get_device): a
-    // rehash frees the old table only after it
+    // the last Get or scan launched on a caller's stream (rf_assoc_get_device,
+    // rf_assoc_scan_device): a rehash frees the old table only after it
     hipEvent_t e_reader = nullptr;
     bool reader_pending = false;
+    StreamScratch sc_scan;  // the scan's live bits and tile counts, handed between streams
     DevBuf tag, keys, vals, count;                                   // the table
     DevBuf b_keys, b_vals, b_exp, b_canon, b_aslot, b_cls, b_rem, b_next, b_cnt, b_status, b_found;  // batch scratch
     AssocView view() {
@@ -2670,10 +2673,45 @@ extern "C" void rf_assoc_destroy(rf_assoc* a) {
         if (a->reader_pending) (void)hipEventSynchronize(a->e_reader);
         (void)hipEventDestroy(a->e_reader);
     }
+    a->sc_scan.destroy();
     for (DevBuf* d : {&a->tag, &a->keys, &a->vals, &a->count, &a->b_keys, &a->b_vals, &a->b_exp, &a->b_canon,
                       &a->b_aslot, &a->b_cls, &a->b_rem, &a->b_next, &a->b_cnt, &a->b_status, &a->b_found})
         d->release();
     delete a;
+}
+
+// Move the table into a fresh one of `cap` slots: every occupied slot
+// (growth), or the live ones only (drop_deleted: rf_assoc_compact).
+static int assoc_rebuild(rf_assoc* a, uint64_t cap, bool drop_deleted) {
+    rf_ctx* ctx = a->ctx;
+    ARG(cap <= (1ull << 31), "assoc table would exceed 2^31 slots");
+    rf_assoc old;  // move the old table out
+    std::swap(old.tag, a->tag);
+    std::swap(old.keys, a->keys);
+    std::swap(old.vals, a->vals);
+    std::swap(old.count, a->count);
+    old.cap = a->cap;
+    hipError_t e = assoc_alloc_table(a, (uint32_t)cap, ctx->stream);
+    if (e != hipSuccess) {  // no room for the new table: the old one stays in place
+        for (DevBuf* d : {&a->tag, &a->keys, &a->vals, &a->count}) d->release();
+        std::swap(old.tag, a->tag);
+        std::swap(old.keys, a->keys);
+        std::swap(old.vals, a->vals);
+        std::swap(old.count, a->count);
+        a->cap = old.cap;
+        return fail(e == hipErrorOutOfMemory ? RF_ENOMEM : RF_EDEVICE, "assoc alloc: %s", hipGetErrorString(e));
+    }
+    HIPC(launch_assoc_rehash(old.view(), old.cap, a->view(), ctx->stream, drop_deleted));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (a->reader_pending) {  // a device-form Get / scan on another stream may still read the old table
+        HIPC(hipEventSynchronize(a->e_reader));
+        a->reader_pending = false;
+    }
+    old.tag.release();
+    old.keys.release();
+    old.vals.release();
+    old.count.release();
+    return RF_OK;
 }
 
 // keep the table at most half full after inserting up to `incoming` new keys
@@ -2686,25 +2724,7 @@ static int assoc_reserve(rf_assoc* a, uint64_t incoming) {
     if (2 * need <= a->cap) return RF_OK;
     uint64_t cap = a->cap;
     while (cap < 2 * need) cap <<= 1;
-    ARG(cap <= (1ull << 31), "assoc table would exceed 2^31 slots");
-    rf_assoc old;  // move the old table out
-    std::swap(old.tag, a->tag);
-    std::swap(old.keys, a->keys);
-    std::swap(old.vals, a->vals);
-    std::swap(old.count, a->count);
-    old.cap = a->cap;
-    HIPC(assoc_alloc_table(a, (uint32_t)cap, ctx->stream));
-    HIPC(launch_assoc_rehash(old.view(), old.cap, a->view(), ctx->stream));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    if (a->reader_pending) {  // a device-form Get on another stream may still read the old table
-        HIPC(hipEventSynchronize(a->e_reader));
-        a->reader_pending = false;
-    }
-    old.tag.release();
-    old.keys.release();
-    old.vals.release();
-    old.count.release();
-    return RF_OK;
+    return assoc_rebuild(a, cap, false);  // deleted keys are carried (rf_assoc_stats' occupied only rises)
 }
 
 // Put over device-resident keys / values / expects (d_status: int32 per op).
@@ -2961,5 +2981,211 @@ extern "C" int rf_assoc_stats(rf_assoc* a, uint64_t* occupied, uint64_t* capacit
     HIPC(sync_copy(a->ctx, &used, a->count.p, 4, hipMemcpyDeviceToHost));
     if (occupied) *occupied = used;
     if (capacity) *capacity = a->cap;
+    return RF_OK;
+}
+
+// ---- scan, compaction, save / restore ---------------------------------------
+// The scan's two steps on stream s (ctx->mu held, so the table stays put
+// between them; the scratch is handed between streams in stream order).
+static int assoc_scan_count(rf_assoc* a, int kind, hipStream_t s, uint64_t* d_n, uint64_t** d_out2) {
+    StreamScratch& sc = a->sc_scan;
+    std::lock_guard<std::mutex> lk(sc.mu);
+    HIPC(sc.acquire(assoc_scan_scratch_bytes(a->cap), s));
+    hipError_t e = launch_assoc_scan_count(a->view(), a->cap, kind, sc.buf.p, d_out2, d_n, s);
+    HIPC(sc.release(s));
+    if (e != hipSuccess) return fail(RF_EDEVICE, "assoc scan: %s", hipGetErrorString(e));
+    return RF_OK;
+}
+
+static int assoc_scan_scatter(rf_assoc* a, hipStream_t s, uint64_t cap_entries, void* d_keys, void* d_vals,
+                              void* d_kinds) {
+    StreamScratch& sc = a->sc_scan;
+    std::lock_guard<std::mutex> lk(sc.mu);
+    HIPC(sc.acquire(assoc_scan_scratch_bytes(a->cap), s));  // (the count's buffer: same size, no reallocation)
+    hipError_t e = launch_assoc_scan_scatter(a->view(), a->cap, sc.buf.p, cap_entries, d_keys, d_vals, d_kinds, s);
+    HIPC(sc.release(s));
+    if (e != hipSuccess) return fail(RF_EDEVICE, "assoc scan: %s", hipGetErrorString(e));
+    return RF_OK;
+}
+
+// {live, deleted} of `kind` on the context's stream; the live bits stay in
+// the scratch for a scatter that follows under the same lock
+static int assoc_count_locked(rf_assoc* a, int kind, uint64_t out2[2]) {
+    uint64_t* d_out2 = nullptr;
+    if (int rc = assoc_scan_count(a, kind, a->ctx->stream, nullptr, &d_out2)) return rc;
+    HIPC(sync_copy(a->ctx, out2, d_out2, 16, hipMemcpyDeviceToHost));
+    return RF_OK;
+}
+
+// the live entries of `kind` (counted just before: n of them) to the host
+static int assoc_rows_locked(rf_assoc* a, uint64_t n, uint8_t* keys32, uint8_t* vals32, int32_t* kinds) {
+    if (!n) return RF_OK;
+    rf_ctx* ctx = a->ctx;
+    hipStream_t s = ctx->stream;
+    HIPC(a->b_keys.ensure(32 * n));
+    HIPC(a->b_vals.ensure(32 * n));
+    if (kinds) HIPC(a->b_status.ensure(4 * n));
+    if (int rc = assoc_scan_scatter(a, s, n, a->b_keys.p, a->b_vals.p, kinds ? a->b_status.p : nullptr)) return rc;
+    HIPC(hipMemcpyAsync(keys32, a->b_keys.p, 32 * n, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(vals32, a->b_vals.p, 32 * n, hipMemcpyDeviceToHost, s));
+    if (kinds) HIPC(hipMemcpyAsync(kinds, a->b_status.p, 4 * n, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return RF_OK;
+}
+
+extern "C" int rf_assoc_count(rf_assoc* a, int kind, uint64_t* live, uint64_t* deleted) {
+    ARG(a, "null assoc");
+    ARG(kind < (1 << 30), "bad assoc kind");
+    std::lock_guard<std::mutex> lk(a->ctx->mu);
+    DevGuard dg(a->ctx->device);
+    uint64_t c[2] = {0, 0};
+    if (int rc = assoc_count_locked(a, kind, c)) return rc;
+    if (live) *live = c[0];
+    if (deleted) *deleted = c[1];
+    return RF_OK;
+}
+
+extern "C" int rf_assoc_scan_device(rf_assoc* a, int kind, uint64_t cap_entries, void* d_keys32, void* d_vals32,
+                                    void* d_kinds, void* d_n, void* stream) {
+    ARG(a && d_n && (cap_entries == 0 || (d_keys32 && d_vals32)), "null argument");
+    ARG(kind < (1 << 30), "bad assoc kind");
+    ARG(kind >= 0 || d_kinds, "a scan of every kind needs the kinds output");
+    std::lock_guard<std::mutex> lk(a->ctx->mu);  // no Put may swap the table meanwhile
+    DevGuard dg(a->ctx->device);
+    hipStream_t s = pick(a->ctx, stream);
+    if (int rc = assoc_scan_count(a, kind, s, static_cast<uint64_t*>(d_n), nullptr)) return rc;
+    if (int rc = assoc_scan_scatter(a, s, cap_entries, d_keys32, d_vals32, d_kinds)) return rc;
+    if (s != a->ctx->stream) {  // (as rf_assoc_get_device: growth and compaction wait for it)
+        if (!a->e_reader) HIPC(hipEventCreateWithFlags(&a->e_reader, hipEventDisableTiming));
+        HIPC(hipEventRecord(a->e_reader, s));
+        a->reader_pending = true;
+    }
+    return RF_OK;
+}
+
+extern "C" int rf_assoc_scan(rf_assoc* a, int kind, uint64_t cap_entries, uint8_t* keys32, uint8_t* vals32,
+                             int32_t* kinds, uint64_t* n) {
+    ARG(a && n && (cap_entries == 0 || (keys32 && vals32)), "null argument");
+    ARG(kind < (1 << 30), "bad assoc kind");
+    ARG(kind >= 0 || kinds, "a scan of every kind needs the kinds output");
+    std::lock_guard<std::mutex> lk(a->ctx->mu);
+    DevGuard dg(a->ctx->device);
+    uint64_t c[2] = {0, 0};
+    if (int rc = assoc_count_locked(a, kind, c)) return rc;
+    *n = c[0];
+    if (c[0] > cap_entries)
+        return fail(RF_EINVAL, "entry buffers too small: need %llu entries", (unsigned long long)c[0]);
+    return assoc_rows_locked(a, c[0], keys32, vals32, kinds);
+}
+
+// capacity = the smallest power of two >= max(1024, 2 * entries)
+static uint64_t assoc_capacity_for(uint64_t entries) {
+    uint64_t cap = 1024;
+    while (cap < 2 * entries) cap <<= 1;
+    return cap;
+}
+
+extern "C" int rf_assoc_compact(rf_assoc* a, uint64_t min_capacity) {
+    ARG(a, "null assoc");
+    ARG(min_capacity < (1ull << 30), "assoc capacity too large");
+    std::lock_guard<std::mutex> lk(a->ctx->mu);
+    DevGuard dg(a->ctx->device);
+    uint64_t c[2] = {0, 0};
+    if (int rc = assoc_count_locked(a, -1, c)) return rc;
+    return assoc_rebuild(a, assoc_capacity_for(std::max(c[0], min_capacity)), true);
+}
+
+namespace {
+struct CFile {
+    FILE* f = nullptr;
+    ~CFile() {
+        if (f) fclose(f);
+    }
+};
+}  // namespace
+
+extern "C" int rf_assoc_save(rf_assoc* a, const char* path) {
+    ARG(a && path && *path, "null argument");
+    rf_ctx* ctx = a->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    uint64_t c[2] = {0, 0};
+    if (int rc = assoc_count_locked(a, -1, c)) return rc;
+    const uint64_t n = c[0];
+    std::vector<int32_t> kinds(n);
+    std::vector<uint8_t> keys(32 * n), vals(32 * n);
+    if (int rc = assoc_rows_locked(a, n, keys.data(), vals.data(), kinds.data())) return rc;
+    // slot order -> (kind, key) order: the file does not depend on the table's history
+    HostPool* pool = ctx_pool(ctx);
+    std::vector<uint32_t> perm(n);
+    std::iota(perm.begin(), perm.end(), 0u);
+    pool_sort(pool, perm.begin(), perm.end(),
+              [&](uint32_t x, uint32_t y) { return assoc_entry_less(kinds.data(), keys.data(), x, y); });
+    std::vector<uint8_t> file(assoc_file_bytes(n, kAssocChunk));
+    if (int rc = assoc_file_write(kinds.data(), keys.data(), vals.data(), perm.data(), n, kAssocChunk, file.data(),
+                                  [&](const uint8_t* b, uint64_t len, uint64_t chunk, uint8_t* out) {
+                                      hash_chunks(pool, b, len, chunk, out);
+                                  }))
+        return rc;
+    // a reader never sees a partial file: written beside it, then renamed (rf_graph_save)
+    const std::string tmp = std::string(path) + ".tmp";
+    CFile out;
+    if (!(out.f = fopen(tmp.c_str(), "wb"))) return fail(RF_EIO, "assoc save: cannot create %s", tmp.c_str());
+    if (fwrite(file.data(), 1, file.size(), out.f) != file.size()) return fail(RF_EIO, "assoc save: write failed");
+    if (fflush(out.f) != 0 || fsync(fileno(out.f)) != 0) return fail(RF_EIO, "assoc save: flush failed");
+    fclose(out.f);
+    out.f = nullptr;
+    if (rename(tmp.c_str(), path) != 0) return fail(RF_EIO, "assoc save: cannot rename to %s", path);
+    return RF_OK;
+}
+
+extern "C" int rf_assoc_restore(rf_ctx* ctx, const char* path, rf_assoc** out) {
+    ARG(ctx && path && out, "null argument");
+    std::vector<uint8_t> file;
+    {
+        CFile in;
+        if (!(in.f = fopen(path, "rb"))) return fail(RF_EIO, "assoc restore: cannot open %s", path);
+        struct stat st;
+        if (fstat(fileno(in.f), &st) != 0 || st.st_size < 0) return fail(RF_EIO, "assoc restore: cannot stat %s", path);
+        // the largest valid file: 2^30 entries and their checksums
+        if ((uint64_t)st.st_size > assoc_file_bytes(kAssocMaxEntries, 64))
+            return fail(RF_EINVAL, "assoc restore: %s is too large for an assoc file", path);
+        file.resize((size_t)st.st_size);
+        if (!file.empty() && fread(file.data(), 1, file.size(), in.f) != file.size())
+            return fail(RF_EIO, "assoc restore: cannot read %s", path);
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    // everything is checked on the host before any of it reaches a kernel
+    HostPool* pool = ctx_pool(ctx);
+    uint64_t n = 0;
+    if (int rc = assoc_file_check(file.data(), file.size(), &n,
+                                  [&](const uint8_t* b, uint64_t len, uint64_t chunk, uint8_t* o) {
+                                      hash_chunks(pool, b, len, chunk, o);
+                                  }))
+        return rc;
+    std::vector<int32_t> kinds(n);
+    std::vector<uint8_t> keys(32 * n), vals(32 * n);
+    assoc_file_unpack(file.data(), n, kinds.data(), keys.data(), vals.data());
+    auto* a = new rf_assoc();
+    std::unique_ptr<rf_assoc, void (*)(rf_assoc*)> guard(a, [](rf_assoc* x) { rf_assoc_destroy(x); });
+    a->ctx = ctx;
+    hipStream_t s = ctx->stream;
+    hipError_t e = assoc_alloc_table(a, (uint32_t)assoc_capacity_for(n), s);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? RF_ENOMEM : RF_EDEVICE, "assoc alloc: %s", hipGetErrorString(e));
+    if (n) {
+        HIPC(a->b_keys.ensure(32 * n));
+        HIPC(a->b_vals.ensure(32 * n));
+        HIPC(a->b_status.ensure(4 * n));
+        HIPC(hipMemcpyAsync(a->b_keys.p, keys.data(), 32 * n, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(a->b_vals.p, vals.data(), 32 * n, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(a->b_status.p, kinds.data(), 4 * n, hipMemcpyHostToDevice, s));
+        HIPC(launch_assoc_load(a->b_status.as<int32_t>(), a->b_keys.as<uint8_t>(), a->b_vals.as<uint8_t>(),
+                               (uint32_t)n, a->view(), s));
+    }
+    HIPC(hipStreamSynchronize(s));
+    guard.release();
+    *out = a;
     return RF_OK;
 }

@@ -303,6 +303,23 @@ hipError_t launch_assoc_abbrev(const AssocView& t, uint32_t kind, uint32_t cap, 
                                const uint8_t* nhex, uint32_t q, uint32_t* matches, uint32_t* hit_slot,
                                hipStream_t s);
 hipError_t launch_iota(uint32_t* out, uint32_t n, hipStream_t s);
-hipError_t launch_assoc_rehash(const AssocView& from, uint32_t cap_from, const AssocView& to, hipStream_t s);
+// drop_deleted: slots whose value is zero are left behind (rf_assoc_compact);
+// the growth path carries them
+hipError_t launch_assoc_rehash(const AssocView& from, uint32_t cap_from, const AssocView& to, hipStream_t s,
+                               bool drop_deleted = false);
+// n dense entries with distinct (kind, key) into an empty table (rf_assoc_restore)
+hipError_t launch_assoc_load(const int32_t* kinds, const uint8_t* keys, const uint8_t* vals, uint32_t n,
+                             const AssocView& to, hipStream_t s);
+// Scan of a cap-slot table (rf_assoc_count / rf_assoc_scan): count marks the
+// live slots of `kind` (< 0: every kind) in scratch
+// [assoc_scan_scratch_bytes(cap)] and leaves {live, deleted} (u64) at *out2
+// inside it (and live at n_out, when given); scatter then writes the live
+// entries in ascending slot order, rows below cap_entries only (kinds_out may
+// be null).
+size_t assoc_scan_scratch_bytes(uint32_t cap);
+hipError_t launch_assoc_scan_count(const AssocView& t, uint32_t cap, int kind, void* scratch, uint64_t** out2,
+                                   uint64_t* n_out, hipStream_t s);
+hipError_t launch_assoc_scan_scatter(const AssocView& t, uint32_t cap, const void* scratch, uint64_t cap_entries,
+                                     void* keys_out, void* vals_out, void* kinds_out, hipStream_t s);
 
 }  // namespace rf

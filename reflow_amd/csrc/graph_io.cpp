@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "graph_internal.h"
+#include "host_par.h"
 
 using namespace rf;
 
@@ -91,19 +92,9 @@ std::vector<Section> sections(rf_graph* gr, std::vector<uint32_t>& lvl, std::vec
 }
 
 // SHA-256 of each kChunk granule of buf[0, n) into out (in order), on the
-// host pool when there is one.
+// host pool when there is one (host_par.h).
 void hash_chunks(rf_ctx* ctx, const uint8_t* buf, uint64_t n, uint8_t* out) {
-    const uint64_t nc = (n + kChunk - 1) / kChunk;
-    HostPool* pool = ctx_pool(ctx);
-    if (!pool || nc < 2) {
-        for (uint64_t c = 0; c < nc; ++c) host_sha256(buf + c * kChunk, std::min(kChunk, n - c * kChunk), out + 32 * c);
-        return;
-    }
-    std::atomic<uint64_t> next{0};
-    pool->run([&](unsigned) {
-        for (uint64_t c; (c = next.fetch_add(1)) < nc;)
-            host_sha256(buf + c * kChunk, std::min(kChunk, n - c * kChunk), out + 32 * c);
-    });
+    rf::hash_chunks(ctx_pool(ctx), buf, n, kChunk, out);
 }
 
 // Consistency checks of a file being restored, section by section, before

@@ -355,24 +355,184 @@ __global__ __launch_bounds__(256) void k5_assoc_abbrev(AssocView t, uint32_t kin
     }
 }
 
-// Rehash every occupied slot into a larger (empty) table; keys are distinct.
+__device__ __forceinline__ bool val_zero(const uint4& a, const uint4& b) {
+    return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0;
+}
+
+// Keys are distinct and nothing compares them in this launch: claim the slot
+// with its final tag, no fences (the kernel boundary publishes).
+__device__ __forceinline__ void assoc_place(const AssocView& to, uint32_t tg, const uint4& lo, const uint4& hi,
+                                            const uint4& vlo, const uint4& vhi) {
+    uint32_t slot = key_hash(lo, hi) & to.mask;
+    while (atomicCAS(&to.tag[slot], kTagEmpty, tg) != kTagEmpty) slot = (slot + 1) & to.mask;
+    to.keys[2ull * slot] = lo;
+    to.keys[2ull * slot + 1] = hi;
+    to.vals[2ull * slot] = vlo;
+    to.vals[2ull * slot + 1] = vhi;
+}
+
+// Rehash every occupied slot into another (empty) table; keys are distinct.
+// kDrop = false (growth): deleted keys keep a slot.  kDrop = true
+// (rf_assoc_compact): slots with a zero value stay behind.
+template <bool kDrop>
 __global__ __launch_bounds__(256) void k5_assoc_rehash(AssocView from, uint32_t cap_from, AssocView to) {
     uint32_t added = 0;
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < cap_from; s += gridDim.x * blockDim.x) {
         const uint32_t tg = from.tag[s];
         if (tg < kTagReady) continue;
-        const uint4 lo = from.keys[2 * s], hi = from.keys[2 * s + 1];
-        // keys are distinct and nothing compares them in this launch: claim
-        // the slot with its final tag, no fences (the kernel boundary publishes)
-        uint32_t slot = key_hash(lo, hi) & to.mask;
-        while (atomicCAS(&to.tag[slot], kTagEmpty, tg) != kTagEmpty) slot = (slot + 1) & to.mask;
-        to.keys[2 * slot] = lo;
-        to.keys[2 * slot + 1] = hi;
-        to.vals[2 * slot] = from.vals[2 * s];
-        to.vals[2 * slot + 1] = from.vals[2 * s + 1];
+        const uint4 vlo = from.vals[2ull * s], vhi = from.vals[2ull * s + 1];
+        if (kDrop && val_zero(vlo, vhi)) continue;
+        assoc_place(to, tg, from.keys[2ull * s], from.keys[2ull * s + 1], vlo, vhi);
         ++added;
     }
     wave_count_add(to.count, added);
+}
+
+// Bulk load of n dense entries (rf_assoc_restore: distinct (kind, key) pairs,
+// checked on the host) into an empty table: the rehash insert, reading from
+// arrays instead of a table.
+__global__ __launch_bounds__(256) void k5_assoc_load(const int32_t* __restrict__ kinds, const uint8_t* __restrict__ keys,
+                                                     const uint8_t* __restrict__ vals, uint32_t n, AssocView to) {
+    uint32_t added = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint4* k = reinterpret_cast<const uint4*>(keys + 32ull * i);
+        const uint4* v = reinterpret_cast<const uint4*>(vals + 32ull * i);
+        assoc_place(to, kTagReady + (uint32_t)kinds[i], k[0], k[1], v[0], v[1]);
+        ++added;
+    }
+    wave_count_add(to.count, added);
+}
+
+// ---------------------------------------------------------------------------
+// Scan (rf_assoc_count / rf_assoc_scan): the live entries of one kind (or of
+// every kind) in ascending slot order, by the tile mark / scan / scatter of
+// k4_collect_*: (1) one pass over the tags and the occupied slots' values
+// writes a live bit per slot (one ballot word per wave and step) and each
+// tile's live and deleted counts; (2) one block scans the tile counts; (3)
+// each tile writes its live entries at its scanned offset.  No counter takes
+// an atomic.  A tile is kScanTile consecutive slots; a table is a power of
+// two >= 1024 slots, so every 64-slot ballot word is whole.
+constexpr uint32_t kScanBlock = 256, kScanPer = 16, kScanTile = kScanBlock * kScanPer;
+
+__global__ __launch_bounds__(kScanBlock) void k5_scan_mark(AssocView t, uint32_t cap, int kind,
+                                                           unsigned long long* __restrict__ live_bits,
+                                                           uint32_t* __restrict__ tile_live,
+                                                           uint32_t* __restrict__ tile_dead) {
+    __shared__ uint32_t s_live[kScanBlock / 64], s_dead[kScanBlock / 64];
+    const uint32_t base = blockIdx.x * kScanTile;  // < cap <= 2^31
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t n_live = 0, n_dead = 0;
+#pragma unroll 4
+    for (uint32_t j = 0; j < kScanPer; ++j) {
+        const uint32_t s = base + j * kScanBlock + threadIdx.x;
+        bool live = false;
+        if (s < cap) {
+            const uint32_t tg = t.tag[s];
+            if (tg >= kTagReady && (kind < 0 || tg == kTagReady + (uint32_t)kind)) {
+                live = !val_zero(t.vals[2ull * s], t.vals[2ull * s + 1]);
+                n_dead += !live;
+            }
+        }
+        const unsigned long long bal = __ballot(live);
+        if (lane == 0 && s < cap) live_bits[s >> 6] = bal;
+        n_live += live;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_live += __shfl_xor(n_live, o, 64);
+        n_dead += __shfl_xor(n_dead, o, 64);
+    }
+    if (lane == 0) {
+        s_live[threadIdx.x >> 6] = n_live;
+        s_dead[threadIdx.x >> 6] = n_dead;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t l = 0, d = 0;
+        for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
+            l += s_live[w];
+            d += s_dead[w];
+        }
+        tile_live[blockIdx.x] = l;
+        tile_dead[blockIdx.x] = d;
+    }
+}
+
+// Exclusive scan of the tiles' live counts by one block (k4_collect_scan's
+// shape); totals -> out2 = {live, deleted}, and live -> *n_out when given.
+__global__ __launch_bounds__(1024) void k5_scan_tiles(uint32_t* __restrict__ tile_live,
+                                                      const uint32_t* __restrict__ tile_dead, uint32_t tiles,
+                                                      unsigned long long* __restrict__ out2,
+                                                      unsigned long long* __restrict__ n_out) {
+    __shared__ uint32_t s_w[16], s_d[16];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0, dead = 0;
+    for (uint32_t b = 0; b < tiles; b += 1024) {
+        const uint32_t i = b + threadIdx.x;
+        const uint32_t c = i < tiles ? tile_live[i] : 0u;
+        uint32_t d = i < tiles ? tile_dead[i] : 0u;
+        uint32_t x = c;  // inclusive wave scan
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= (uint32_t)o) x += y;
+        }
+        for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+        if (lane == 63) s_w[wave] = x;
+        if (lane == 0) s_d[wave] = d;
+        __syncthreads();
+        uint32_t before = 0, total = 0, dtotal = 0;
+        for (uint32_t w = 0; w < 16; ++w) {
+            before += w < wave ? s_w[w] : 0u;
+            total += s_w[w];
+            dtotal += s_d[w];
+        }
+        if (i < tiles) tile_live[i] = (uint32_t)(carry + before + x - c);  // < 2^31: at most cap entries
+        carry += total;
+        dead += dtotal;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out2[0] = carry;
+        out2[1] = dead;
+        if (n_out) *n_out = carry;
+    }
+}
+
+// Each tile's live entries to rows [tile_off, ...) of the outputs, ascending
+// by slot; a row at or past cap_entries is counted (above) but not stored.
+__global__ __launch_bounds__(kScanBlock) void k5_scan_scatter(AssocView t, uint32_t cap,
+                                                              const unsigned long long* __restrict__ live_bits,
+                                                              const uint32_t* __restrict__ tile_off,
+                                                              uint64_t cap_entries, uint4* __restrict__ keys_out,
+                                                              uint4* __restrict__ vals_out,
+                                                              int32_t* __restrict__ kinds_out) {
+    __shared__ uint32_t s_w[kScanBlock / 64];
+    const uint32_t base = blockIdx.x * kScanTile;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    uint64_t run = tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kScanPer; ++j) {
+        const uint32_t s = base + j * kScanBlock + threadIdx.x;
+        const unsigned long long bal = s < cap ? live_bits[s >> 6] : 0ull;  // wave-uniform
+        if (lane == 0) s_w[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
+            before += w < wave ? s_w[w] : 0;
+            total += s_w[w];
+        }
+        if ((bal >> lane) & 1ull) {
+            const uint64_t o = run + before + (uint32_t)__popcll(bal & lt);
+            if (o < cap_entries) {
+                keys_out[2 * o] = t.keys[2ull * s];
+                keys_out[2 * o + 1] = t.keys[2ull * s + 1];
+                vals_out[2 * o] = t.vals[2ull * s];
+                vals_out[2 * o + 1] = t.vals[2ull * s + 1];
+                if (kinds_out) kinds_out[o] = (int32_t)(t.tag[s] - kTagReady);
+            }
+        }
+        run += total;
+        __syncthreads();
+    }
 }
 
 // rem[q] = q: a Put batch's first round holds every op, in index order
@@ -432,8 +592,60 @@ hipError_t launch_iota(uint32_t* out, uint32_t n, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_assoc_rehash(const AssocView& from, uint32_t cap_from, const AssocView& to, hipStream_t s) {
-    hipLaunchKernelGGL(k5_assoc_rehash, dim3(grid256(cap_from)), dim3(256), 0, s, from, cap_from, to);
+hipError_t launch_assoc_rehash(const AssocView& from, uint32_t cap_from, const AssocView& to, hipStream_t s,
+                               bool drop_deleted) {
+    if (drop_deleted)
+        hipLaunchKernelGGL(k5_assoc_rehash<true>, dim3(grid256(cap_from)), dim3(256), 0, s, from, cap_from, to);
+    else
+        hipLaunchKernelGGL(k5_assoc_rehash<false>, dim3(grid256(cap_from)), dim3(256), 0, s, from, cap_from, to);
+    return hipGetLastError();
+}
+
+hipError_t launch_assoc_load(const int32_t* kinds, const uint8_t* keys, const uint8_t* vals, uint32_t n,
+                             const AssocView& to, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k5_assoc_load, dim3(grid256(n)), dim3(256), 0, s, kinds, keys, vals, n, to);
+    return hipGetLastError();
+}
+
+uint32_t assoc_scan_tiles(uint32_t cap) { return (uint32_t)(((uint64_t)cap + kScanTile - 1) / kScanTile); }
+
+size_t assoc_scan_scratch_bytes(uint32_t cap) {
+    return 8 * (((size_t)cap + 63) / 64) + 8 * (size_t)assoc_scan_tiles(cap) + 16;
+}
+
+// scratch layout: live bits (a u64 per 64 slots), out2 {live, deleted}, the
+// tiles' live counts (their offsets after the scan), the tiles' deleted counts
+static void scan_scratch(void* scratch, uint32_t cap, unsigned long long** bits, unsigned long long** out2,
+                         uint32_t** tile_live, uint32_t** tile_dead) {
+    *bits = static_cast<unsigned long long*>(scratch);
+    *out2 = *bits + ((size_t)cap + 63) / 64;
+    *tile_live = reinterpret_cast<uint32_t*>(*out2 + 2);
+    *tile_dead = *tile_live + assoc_scan_tiles(cap);
+}
+
+hipError_t launch_assoc_scan_count(const AssocView& t, uint32_t cap, int kind, void* scratch, uint64_t** out2,
+                                   uint64_t* n_out, hipStream_t s) {
+    unsigned long long *bits, *o2;
+    uint32_t *tl, *td;
+    scan_scratch(scratch, cap, &bits, &o2, &tl, &td);
+    const uint32_t tiles = assoc_scan_tiles(cap);
+    hipLaunchKernelGGL(k5_scan_mark, dim3(tiles), dim3(kScanBlock), 0, s, t, cap, kind, bits, tl, td);
+    hipLaunchKernelGGL(k5_scan_tiles, dim3(1), dim3(1024), 0, s, tl, td, tiles, o2,
+                       reinterpret_cast<unsigned long long*>(n_out));
+    if (out2) *out2 = reinterpret_cast<uint64_t*>(o2);
+    return hipGetLastError();
+}
+
+hipError_t launch_assoc_scan_scatter(const AssocView& t, uint32_t cap, const void* scratch, uint64_t cap_entries,
+                                     void* keys_out, void* vals_out, void* kinds_out, hipStream_t s) {
+    if (!cap_entries) return hipSuccess;  // nothing may be stored
+    unsigned long long *bits, *o2;
+    uint32_t *tl, *td;
+    scan_scratch(const_cast<void*>(scratch), cap, &bits, &o2, &tl, &td);
+    hipLaunchKernelGGL(k5_scan_scatter, dim3(assoc_scan_tiles(cap)), dim3(kScanBlock), 0, s, t, cap, bits, tl,
+                       cap_entries, static_cast<uint4*>(keys_out), static_cast<uint4*>(vals_out),
+                       static_cast<int32_t*>(kinds_out));
     return hipGetLastError();
 }
 

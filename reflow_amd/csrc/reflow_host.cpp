@@ -1201,6 +1201,49 @@ std::pair<Digest, Digest> Assoc::GetAbbrev(AssocKind kind, const std::string& he
     return {ko, vo};
 }
 
+std::pair<uint64_t, uint64_t> Assoc::Count(int kind) {
+    uint64_t live = 0, deleted = 0;
+    Check(rf_assoc_count(a_, kind, &live, &deleted));
+    return {live, deleted};
+}
+
+std::vector<Assoc::Entry> Assoc::Scan(int kind) {
+    // the table may change between the count and the scan: retry with the size the scan reports
+    uint64_t n = Count(kind).first;
+    std::vector<Digest> keys, vals;
+    std::vector<int32_t> kinds;
+    for (;;) {
+        const uint64_t cap = n;
+        keys.resize(cap);
+        vals.resize(cap);
+        kinds.resize(cap + 1);
+        const int rc = rf_assoc_scan(a_, kind, cap, cap ? keys[0].b.data() : nullptr, cap ? vals[0].b.data() : nullptr,
+                                     kinds.data(), &n);
+        if (rc == RF_EINVAL && n > cap) continue;
+        Check(rc);
+        break;
+    }
+    std::vector<Entry> out(n);
+    for (uint64_t i = 0; i < n; ++i) out[i] = Entry{kinds[i], keys[i], vals[i]};
+    return out;
+}
+
+void Assoc::Compact(uint64_t min_capacity) { Check(rf_assoc_compact(a_, min_capacity)); }
+
+void Assoc::Save(const std::string& path) { Check(rf_assoc_save(a_, path.c_str())); }
+
+std::unique_ptr<Assoc> Assoc::Restore(Engine& e, const std::string& path) {
+    std::unique_ptr<Assoc> a(new Assoc());
+    Check(rf_assoc_restore(e.ctx(), path.c_str(), &a->a_));
+    return a;
+}
+
+std::pair<uint64_t, uint64_t> Assoc::Stats() {
+    uint64_t occ = 0, cap = 0;
+    Check(rf_assoc_stats(a_, &occ, &cap));
+    return {occ, cap};
+}
+
 void Delete(Assoc& a, AssocKind kind, const Digest& k) { a.Put(kind, Digest{}, k, Digest{}); }
 
 }  // namespace reflow
