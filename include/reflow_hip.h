@@ -88,11 +88,15 @@ int rf_host_info(rf_ctx *ctx, int *threads, double *core_bytes_per_s, int *sha_e
  * bench.py prices the host leg against. */
 int rf_host_rate(rf_ctx *ctx, int *ways, double *thread_bytes_per_s);
 /* The feed rate (bytes/s) the K1 planner prices the host leg's HBM-resident
- * bytes at: measured by the last plan run on this context whose host leg took
- * >= 1 GiB at the current width (*measured = 1; the leg's bytes over its wall
- * time, D2H copies and SHA-NI threads together), else the built-in PCIe Gen5
- * estimate (52 GB/s, *measured = 0).  Plans created after a measurement use
- * it: a caller calibrates with one RF_SHA_ALL_HOST run, then plans the split. */
+ * bytes at: measured by the last RF_SHA_ALL_HOST plan run on this context
+ * whose host leg took >= 1 GiB at the current width (*measured = 1; the leg's
+ * bytes over its wall time, D2H copies and SHA-NI threads together), else the
+ * built-in PCIe Gen5 estimate (52 GB/s, *measured = 0).  Only all-host runs
+ * calibrate: a hybrid run's host leg may idle beside the GPU legs or start
+ * files from a GPU-made prefix, and a host-resident batch crosses no link, so
+ * their bytes over wall time are not the feed rate and leave it as it was.
+ * Plans created after a measurement use it: a caller calibrates with one
+ * RF_SHA_ALL_HOST run, then plans the split. */
 int rf_host_link(rf_ctx *ctx, double *bytes_per_s, int *measured);
 
 /* ---- device memory and timing -------------------------------------------
@@ -169,6 +173,33 @@ void rf_sha_plan_destroy(rf_sha_plan *plan);
 #define RF_SHA_NO_OCTO 16u     /* small sets: no eight-per-wave two-lane chains (pair or lanes) */
 #define RF_SHA_ALL_HOST 32u    /* every message on the host leg (needs SHA-NI and host threads) */
 #define RF_SHA_NO_HOST 64u     /* no host leg: every message on the GPU kernels */
+#define RF_SHA_NO_PREFIX 128u  /* no prefix hand-over: the split and the run as without it */
+
+/* Prefix hand-over.  A host-leg message that waits in the pool's queue has
+ * its first blocks hashed by an idle duo wave meanwhile; the host thread that
+ * claims it looks once whether the wave is done and, if so, resumes from the
+ * wave's chaining value instead of block 0 (it never waits for the wave).
+ * Planned for HBM-resident plans with both legs; off with RF_SHA_NO_PREFIX,
+ * or with RF_SHA_PREFIX=0 in the environment when the plan is created
+ * (RF_SHA_PREFIX_ALPHA there sets the share of a message's modelled wait its
+ * prefix is sized to, default 0.85). */
+typedef struct {
+    uint64_t n_prefixed;    /* host-leg messages with a prefix                 */
+    uint64_t planned_bytes; /* 64 x their prefix blocks                        */
+    uint64_t taken, missed; /* last run: prefixes found ready / not ready      */
+    uint64_t skipped_bytes; /* last run: bytes the host leg did not hash       */
+} rf_sha_prefix_stats;
+int rf_sha_plan_prefix_stats(rf_sha_plan *plan, rf_sha_prefix_stats *out);
+/* Test control.  prefix_blocks[i] (NULL: keep the plan's) replaces the prefix
+ * of host-leg message i -- the plan's host messages in its own order, largest
+ * first, n_host of them -- each at most len / 64.  mode: RF_PREFIX_RACE, the
+ * production behaviour; RF_PREFIX_WAIT, the host leg starts only once the
+ * prefix launch is done (an event wait), so every prefix is taken;
+ * RF_PREFIX_MISS, the prefixes are left out of the launch, so none is. */
+#define RF_PREFIX_RACE 0
+#define RF_PREFIX_WAIT 1
+#define RF_PREFIX_MISS 2
+int rf_sha_plan_set_prefixes(rf_sha_plan *plan, const uint64_t *prefix_blocks, int mode);
 
 /* ---- Streaming SHA-256 (Digester.NewWriter: an io.Writer whose state carries
  * across Write calls) for many streams at once -------------------------------

@@ -22,12 +22,14 @@ RF_SHA_NO_PAIR = 8
 RF_SHA_NO_OCTO = 16
 RF_SHA_ALL_HOST = 32
 RF_SHA_NO_HOST = 64
+RF_SHA_NO_PREFIX = 128
+RF_PREFIX_RACE, RF_PREFIX_WAIT, RF_PREFIX_MISS = 0, 1, 2
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
     "rf_init", "rf_destroy", "rf_last_error", "rf_device_count", "rf_device_cus", "rf_sync", "rf_version",
     "rf_sha256_batch", "rf_sha256_arena", "rf_sha_plan_create", "rf_sha_plan_run",
-    "rf_sha_plan_stats", "rf_sha_plan_destroy", "rf_gen_fill", "rf_fileset_digest_batch",
+    "rf_sha_plan_stats", "rf_sha_plan_destroy", "rf_sha_plan_prefix_stats", "rf_sha_plan_set_prefixes", "rf_gen_fill", "rf_fileset_digest_batch",
     "rf_fileset_digest_device", "rf_install_dir", "rf_install_info", "rf_install_entries",
     "rf_install_destroy",
     "rf_graph_load", "rf_graph_destroy", "rf_graph_set_slots", "rf_graph_set_slots_device",
@@ -63,6 +65,12 @@ class RfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rf error %d: %s" % (code, msg))
         self.code = code
+
+
+class ShaPrefixStats(ctypes.Structure):
+    """rf_sha_prefix_stats: the plan's prefix hand-overs and what the last run's host leg made of them."""
+    _fields_ = [("n_prefixed", ctypes.c_uint64), ("planned_bytes", ctypes.c_uint64), ("taken", ctypes.c_uint64),
+                ("missed", ctypes.c_uint64), ("skipped_bytes", ctypes.c_uint64)]
 
 
 class ShaStats(ctypes.Structure):
@@ -289,6 +297,7 @@ def lib():
             "rf_sha_plan_create": ([vp, vp, vp, u64, u32, vp], i32),
             "rf_sha_plan_run": ([vp, vp, vp, vp], i32),
             "rf_sha_plan_stats": ([vp, vp], i32), "rf_sha_plan_destroy": ([vp], None),
+            "rf_sha_plan_prefix_stats": ([vp, vp], i32), "rf_sha_plan_set_prefixes": ([vp, vp, i32], i32),
             "rf_gen_fill": ([vp, vp, vp, vp, u64, u64, u64, vp], i32),
             "rf_fileset_digest_batch": ([vp, u64, vp, vp, vp, vp, vp, vp], i32),
             "rf_fileset_digest_device": ([vp, u64, vp, vp, vp, vp, vp, vp], i32),
@@ -763,6 +772,17 @@ class ShaPlan:
         s = ShaStats()
         _check(lib().rf_sha_plan_stats(self._h, ctypes.byref(s)))
         return s
+
+    def prefix_stats(self) -> ShaPrefixStats:
+        s = ShaPrefixStats()
+        _check(lib().rf_sha_plan_prefix_stats(self._h, ctypes.byref(s)))
+        return s
+
+    def set_prefixes(self, prefix_blocks, mode=RF_PREFIX_RACE):
+        """Test control: prefix_blocks[i] for host task i (largest first; None keeps
+        the planner's) and how the run treats them (RF_PREFIX_RACE / WAIT / MISS)."""
+        pb = None if prefix_blocks is None else np.ascontiguousarray(prefix_blocks, dtype=np.uint64)
+        _check(lib().rf_sha_plan_set_prefixes(self._h, None if pb is None else pb.ctypes.data, mode))
 
     def close(self):
         if self._h:

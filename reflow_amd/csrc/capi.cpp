@@ -34,6 +34,7 @@
 
 #include "engine.h"
 #include "host_leg.h"
+#include "host_sched.h"
 #include "ctx.h"
 #include "assoc_io.h"
 #include "graph_internal.h"
@@ -310,6 +311,19 @@ struct rf_sha_plan {
     hipEvent_t e0 = nullptr, e_solo = nullptr, e_lanes = nullptr, e1 = nullptr;
     bool ran = false;
     rf_sha_stats st{};
+    // prefix hand-over (host_sched.h): pfx[i] = blocks of host task i a duo
+    // wave hashes first; hand = coherent pinned host memory, 32-byte chaining
+    // values for every host task, then their 4-byte ready flags
+    uint32_t flags = 0;
+    std::vector<uint64_t> pfx;
+    uint32_t n_pfx = 0;
+    int pfx_mode = RF_PREFIX_RACE;
+    DevBuf d_pfx_ids, d_pfx_blocks, d_pfx_slot;
+    void* hand = nullptr;
+    size_t hand_cap = 0;  // host tasks it holds
+    bool side_ran = false;      // the last run launched on the side stream
+    bool side_pending = false;  // ... and e_solo has not been waited for since
+    HostLegStats pfx_last{};
 };
 
 // Measured per-block chain latencies of the GPU legs:
@@ -378,6 +392,21 @@ struct HostModel {
 static constexpr double kD2HLink = 52e9;
 static constexpr uint64_t kLinkCalibBytes = 1ull << 30;  // a host leg this large calibrates the link
 
+// Prefix hand-over (host_sched.h, DESIGN.md §5 "Prefix hand-over").
+//   kDuoBlockS        the duo chain's measured time per block (gpu_model's t_duo).
+//   kPrefixAlpha      the share of a message's modelled wait its prefix is sized
+//                     to: the wave must be done when the host claims the message,
+//                     and a host leg that runs ahead of its model claims early,
+//                     so 15 % of the wait is kept as slack.  A miss loses
+//                     nothing but the wave's work.
+//   kPrefixMinBlocks  below 4096 blocks (256 KiB, ~160 us of one host lane) a
+//                     prefix saves about what the model charges per message and
+//                     per pool wake (20 + 100 us): inside the model's own error,
+//                     so it is not worth a workgroup and a flag.
+static constexpr double kDuoBlockS = 1.13e-6;
+static constexpr double kPrefixAlpha = 0.85;
+static constexpr uint64_t kPrefixMinBlocks = 4096;
+
 // The feed rate the planner prices the host leg's HBM-resident bytes at:
 // the context's last measurement at the current width (a whole leg's bytes
 // over its wall time: the D2H copies and the SHA-NI threads together), else
@@ -407,9 +436,15 @@ extern "C" int rf_host_link(rf_ctx* ctx, double* bytes_per_s, int* measured) {
 // the best h sits at their crossing; the smallest h reaching the best
 // makespan (2% margin) wins, so the GPU keeps every message the host leg
 // would not finish sooner.
+//
+// With a schedule model (hs: prefix hand-over on), host(h) is instead the
+// thread-aware replay of the pool (host_sched.h) with each message's prefix
+// taken off its bytes, and prefix_out receives the h host messages' prefixes.
+// Without one the split is exactly the per-slot model above.
 static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, std::vector<uint32_t>& order,
                        uint32_t n_cu, uint32_t flags, const HostModel& hm, uint32_t* n_host_out,
-                       uint32_t* n_solo_out) {
+                       uint32_t* n_solo_out, const HostSchedParams* hs = nullptr,
+                       std::vector<uint64_t>* prefix_out = nullptr) {
     const uint64_t n = nb.size();
     order.resize(n);
     std::iota(order.begin(), order.end(), 0u);
@@ -423,10 +458,19 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
     if (host_ok && (flags & RF_SHA_ALL_HOST)) {
         h = n;
     } else if (host_ok && n) {
-        std::vector<double> host_t(n + 1, 0.0);
+        std::vector<double> host_t(n + 1, hs ? -1.0 : 0.0);
         std::vector<double> load(hm.slots, 0.0);  // min-heap of slot loads (s)
         double maxload = 0, bytes = 0;
-        for (uint64_t i = 0; i < n; ++i) {
+        std::vector<uint64_t> slens;
+        if (hs) {
+            slens.resize(n);
+            for (uint64_t i = 0; i < n; ++i) slens[i] = lens[order[i]];
+        }
+        auto host_at = [&](uint64_t x) {
+            if (host_t[x] < 0) host_t[x] = x ? host_schedule(slens.data(), x, *hs).makespan : 0.0;
+            return host_t[x];
+        };
+        for (uint64_t i = 0; i < n && !hs; ++i) {
             std::pop_heap(load.begin(), load.end(), std::greater<double>());
             load.back() += (double)lens[order[i]] / hm.rate + 20e-6;
             maxload = std::max(maxload, load.back());
@@ -446,21 +490,25 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
         uint64_t lo = 0, hi = n;
         while (lo < hi) {
             const uint64_t mid = (lo + hi) / 2;
-            if (host_t[mid] >= gpu_t(mid)) hi = mid; else lo = mid + 1;
+            if (host_at(mid) >= gpu_t(mid)) hi = mid; else lo = mid + 1;
         }
         const uint64_t x0 = lo;
         double best = gpu_t(0);
         uint64_t best_h = 0;
         for (uint64_t c : {x0 > 0 ? x0 - 1 : 0, x0}) {
-            const double m = std::max(host_t[c], gpu_t(c));
-            if (m < best * 0.98) {
+            const double m = std::max(host_at(c), gpu_t(c));
+            // With prefixes the message at the crossing costs the host only
+            // its suffix, and a duo wave that hashes it whole ends after the
+            // host leg: once a host leg is chosen, one more message joins it
+            // whenever the model has that no slower (no 2 % margin).
+            if (m < best * 0.98 || (hs && best_h > 0 && m <= best)) {
                 best = m;
                 best_h = c;
             }
         }
         // the smallest h with the same makespan (gpu_t is a step function
         // of h: below the crossing the host leg only adds threads' work)
-        if (best_h > 0 && host_t[best_h] < gpu_t(best_h)) {
+        if (best_h > 0 && host_at(best_h) < gpu_t(best_h)) {
             const double target = gpu_t(best_h);
             uint64_t a = 0, b = best_h;
             while (a < b) {
@@ -470,6 +518,7 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
             best_h = a;
         }
         h = best_h;
+        if (hs && prefix_out) *prefix_out = host_schedule(slens.data(), h, *hs).prefix_blocks;
     }
     uint64_t k = 0;
     gpu_model(nbs, suf, h, n_cu, flags, &k);
@@ -485,6 +534,59 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
 }
 
 extern "C" void rf_sha_plan_destroy(rf_sha_plan* p);
+
+// The side stream's last launch may still write chaining values and flags.
+static hipError_t plan_wait_side(rf_sha_plan* p) {
+    if (!p->side_pending) return hipSuccess;
+    p->side_pending = false;
+    return hipEventSynchronize(p->e_solo);
+}
+
+// Installs prefix[i] for host task i (all zero: none): the launch's device
+// arrays, and the host tasks' pointers into the hand-over memory.
+static int plan_prefixes(rf_sha_plan* p, const uint64_t* prefix) {
+    const uint32_t nh = p->n_host;
+    HIPC(plan_wait_side(p));
+    p->pfx.assign(prefix, prefix + nh);
+    std::vector<uint32_t> ids, slot;
+    std::vector<uint64_t> blocks;
+    for (uint32_t i = 0; i < nh; ++i) {
+        p->host[i].prefix_blocks = 0;
+        p->host[i].mid = p->host[i].ready = nullptr;
+        if (!prefix[i]) continue;
+        ids.push_back(p->host[i].id);
+        blocks.push_back(prefix[i]);
+        slot.push_back(i);
+    }
+    p->n_pfx = (uint32_t)ids.size();
+    p->pfx_last = HostLegStats{};
+    if (!p->n_pfx) return RF_OK;
+    if (p->hand_cap < nh) {
+        if (p->hand) HIPC(hipHostFree(p->hand));
+        p->hand = nullptr;
+        p->hand_cap = 0;
+        const size_t want = std::max<size_t>(nh, 128);
+        HIPC(hipHostMalloc(&p->hand, 36 * want, hipHostMallocCoherent | hipHostMallocMapped));
+        p->hand_cap = want;
+    }
+    const uint32_t* mid = static_cast<const uint32_t*>(p->hand);
+    const uint32_t* ready = mid + 8 * p->hand_cap;
+    for (uint32_t j = 0; j < p->n_pfx; ++j) {
+        HostTask& t = p->host[slot[j]];
+        t.prefix_blocks = blocks[j];
+        t.mid = mid + 8ull * slot[j];
+        t.ready = ready + slot[j];
+    }
+    hipError_t e;
+    if ((e = p->d_pfx_ids.ensure(4ull * p->n_pfx)) != hipSuccess ||
+        (e = p->d_pfx_blocks.ensure(8ull * p->n_pfx)) != hipSuccess ||
+        (e = p->d_pfx_slot.ensure(4ull * p->n_pfx)) != hipSuccess)
+        return fail(RF_ENOMEM, "plan alloc: %s", hipGetErrorString(e));
+    HIPC(sync_copy(p->ctx, p->d_pfx_ids.p, ids.data(), 4ull * p->n_pfx, hipMemcpyHostToDevice));
+    HIPC(sync_copy(p->ctx, p->d_pfx_blocks.p, blocks.data(), 8ull * p->n_pfx, hipMemcpyHostToDevice));
+    HIPC(sync_copy(p->ctx, p->d_pfx_slot.p, slot.data(), 4ull * p->n_pfx, hipMemcpyHostToDevice));
+    return RF_OK;
+}
 
 // Fills plan p for (offs, lens): host-side split, device copies of the
 // offsets/lengths/order (buffers only grow), stream and events created once.
@@ -518,7 +620,27 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
     p->st = rf_sha_stats{};
     std::vector<uint32_t> order;
     uint32_t n_solo = 0, n_host = 0;
-    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo);
+    // Prefix hand-over: for plans that run from HBM with both legs and the
+    // two-lane chain kernel (a host-resident message would first have to be
+    // uploaded for its prefix).  RF_SHA_PREFIX=0 in the environment and
+    // RF_SHA_NO_PREFIX give the split and the run without it.
+    HostSchedParams hs;
+    std::vector<uint64_t> prefix;
+    const char* env_pfx = getenv("RF_SHA_PREFIX");
+    const bool prefix_on = !host_resident && threads > 0 && !(env_pfx && atoi(env_pfx) == 0) &&
+                           !(flags & (RF_SHA_NO_PREFIX | RF_SHA_ALL_HOST | RF_SHA_NO_HOST | RF_SHA_ONE_LANE_CHAIN));
+    if (prefix_on) {
+        hs.threads = threads;
+        hs.ways = ways;
+        for (int k = 1; k <= ways; ++k) hs.lane_rate[k - 1] = host_sha_rate(k) / k;
+        hs.link = hm.link;
+        hs.t_duo = kDuoBlockS;
+        hs.alpha = kPrefixAlpha;
+        if (const char* a = getenv("RF_SHA_PREFIX_ALPHA")) hs.alpha = std::min(1.0, std::max(0.0, atof(a)));
+        hs.min_blocks = kPrefixMinBlocks;
+    }
+    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo, prefix_on ? &hs : nullptr, &prefix);
+    p->flags = flags;
     p->n_host = n_host;
     p->n_solo = n_solo;
     p->duo = !(flags & RF_SHA_ONE_LANE_CHAIN);
@@ -571,7 +693,8 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
     p->st.total_blocks = total_blocks;
     p->st.max_blocks = max_blocks;
     p->st.total_bytes = total_bytes;
-    return RF_OK;
+    prefix.resize(n_host, 0);
+    return plan_prefixes(p, prefix.data());
 }
 
 static int plan_create_nolock(rf_ctx* ctx, const uint64_t* offs, const uint64_t* lens, uint64_t n,
@@ -619,13 +742,31 @@ static int plan_run_locked(rf_sha_plan* p, const void* d_arena, void* d_out, hip
     HIPC(hipEventRecord(p->e0, s));
     const uint32_t* order = p->d_order.as<uint32_t>();
     if (p->n_lanes) HIPC(hipMemsetAsync(p->d_heads.p, 0, 4 * 64, s));
-    if (p->n_solo) {
+    // prefix hand-overs ride in the duo launch (RF_PREFIX_MISS: left out, so
+    // every flag stays unset); the flags are reset here, on the host, once the
+    // previous run's launch can no longer set one
+    const bool pfx_launch = p->n_pfx && !h_arena && p->pfx_mode != RF_PREFIX_MISS;
+    if (p->n_pfx) {
+        HIPC(plan_wait_side(p));
+        memset(static_cast<uint32_t*>(p->hand) + 8 * p->hand_cap, 0, 4 * p->hand_cap);
+    }
+    p->side_ran = p->n_solo || pfx_launch;
+    if (p->side_ran) {
         HIPC(hipStreamWaitEvent(p->side, p->e0, 0));
         SoloArgs sa{static_cast<const uint8_t*>(d_arena), p->d_offs.as<uint64_t>(),
                     p->d_lens.as<uint64_t>(), order + p->n_lanes, p->n_solo,
                     static_cast<uint8_t*>(d_out)};
-        HIPC(launch_sha_solo(sa, p->duo, p->side));
+        if (pfx_launch) {
+            void* d_hand = nullptr;
+            HIPC(hipHostGetDevicePointer(&d_hand, p->hand, 0));
+            PrefixArgs pa{p->d_pfx_ids.as<uint32_t>(), p->d_pfx_blocks.as<uint64_t>(), p->d_pfx_slot.as<uint32_t>(),
+                          p->n_pfx, static_cast<uint32_t*>(d_hand), static_cast<uint32_t*>(d_hand) + 8 * p->hand_cap};
+            HIPC(launch_sha_duo_prefix(sa, pa, p->side));
+        } else {
+            HIPC(launch_sha_solo(sa, p->duo, p->side));
+        }
         HIPC(hipEventRecord(p->e_solo, p->side));
+        p->side_pending = true;
     }
     if (p->n_lanes && p->octo) {
         SoloArgs oa{static_cast<const uint8_t*>(d_arena), p->d_offs.as<uint64_t>(), p->d_lens.as<uint64_t>(),
@@ -653,16 +794,22 @@ static int plan_run_locked(rf_sha_plan* p, const void* d_arena, void* d_out, hip
         // the arena's bytes are written once the work queued on s before e0
         // is done (a host-side wait: see HostPool::Stage on stream-side waits)
         if (!h_arena) HIPC(hipEventSynchronize(p->e0));
+        // RF_PREFIX_WAIT (tests): every prefix is ready before the leg starts
+        if (pfx_launch && p->pfx_mode == RF_PREFIX_WAIT) HIPC(plan_wait_side(p));
         const auto t0 = std::chrono::steady_clock::now();
         std::string err;
         if (ctx_lock) ctx_lock->unlock();
         const bool ok = host_leg_run(*pool, p->host.data(), p->n_host,
                                      h_arena ? nullptr : static_cast<const uint8_t*>(d_arena), h_arena,
-                                     p->h_host_dig.bytes(), &err);
+                                     p->h_host_dig.bytes(), &err, &p->pfx_last);
         if (ctx_lock) ctx_lock->lock();
         if (!ok) return fail(RF_EDEVICE, "%s", err.c_str());
         p->last_ms_host = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (!h_arena && p->st.host_bytes >= kLinkCalibBytes && p->last_ms_host > 0) {  // calibrate the link
+        // calibrate the link: all-host runs only -- a hybrid leg's bytes over
+        // its wall time is not its feed rate (it may idle beside the GPU legs,
+        // and prefixes take bytes off it)
+        if (!h_arena && (p->flags & RF_SHA_ALL_HOST) && !p->n_pfx && p->st.host_bytes >= kLinkCalibBytes &&
+            p->last_ms_host > 0) {
             p->ctx->host_link_bps = (double)p->st.host_bytes / (p->last_ms_host * 1e-3);
             p->ctx->host_link_threads = (unsigned)pool->size();
         }
@@ -672,7 +819,7 @@ static int plan_run_locked(rf_sha_plan* p, const void* d_arena, void* d_out, hip
         HIPC(launch_scatter_digests(static_cast<uint8_t*>(d_out), p->d_host_ids.as<uint32_t>(),
                                     p->d_host_dig.as<uint8_t>(), p->n_host, s));
     }
-    if (p->n_solo) HIPC(hipStreamWaitEvent(s, p->e_solo, 0));
+    if (p->side_ran) HIPC(hipStreamWaitEvent(s, p->e_solo, 0));
     HIPC(hipEventRecord(p->e1, s));
     p->ran = true;
     return RF_OK;
@@ -697,7 +844,7 @@ extern "C" int rf_sha_plan_stats(rf_sha_plan* p, rf_sha_stats* out) {
         p->st.last_ms_total = ms;
         HIPC(hipEventElapsedTime(&ms, p->e0, p->e_lanes));
         p->st.last_ms_lanes = p->n_lanes ? ms : 0.f;
-        if (p->n_solo) {
+        if (p->side_ran) {
             HIPC(hipEventElapsedTime(&ms, p->e0, p->e_solo));
             p->st.last_ms_solo = ms;
         } else {
@@ -706,6 +853,37 @@ extern "C" int rf_sha_plan_stats(rf_sha_plan* p, rf_sha_stats* out) {
         p->st.last_ms_host = p->last_ms_host;
     }
     *out = p->st;
+    return RF_OK;
+}
+
+extern "C" int rf_sha_plan_prefix_stats(rf_sha_plan* p, rf_sha_prefix_stats* out) {
+    ARG(p && out, "null argument");
+    std::lock_guard<std::mutex> plk(p->mu);
+    out->n_prefixed = p->n_pfx;
+    out->planned_bytes = 0;
+    for (uint64_t b : p->pfx) out->planned_bytes += 64 * b;
+    out->taken = p->pfx_last.taken;
+    out->missed = p->pfx_last.missed;
+    out->skipped_bytes = p->pfx_last.skipped_bytes;
+    return RF_OK;
+}
+
+extern "C" int rf_sha_plan_set_prefixes(rf_sha_plan* p, const uint64_t* prefix_blocks, int mode) {
+    ARG(p, "null plan");
+    ARG(mode == RF_PREFIX_RACE || mode == RF_PREFIX_WAIT || mode == RF_PREFIX_MISS, "unknown prefix mode");
+    std::lock_guard<std::mutex> plk(p->mu);
+    std::lock_guard<std::mutex> lk(p->ctx->mu);
+    DevGuard g(p->ctx->device);
+    if (prefix_blocks) {
+        ARG(p->duo, "prefixes need the two-lane chain kernel (no RF_SHA_ONE_LANE_CHAIN)");
+        for (uint32_t i = 0; i < p->n_host; ++i)
+            if (prefix_blocks[i] > p->host[i].len / 64)
+                return fail(RF_EINVAL, "prefix_blocks[%u] = %llu exceeds the message's %llu whole blocks", i,
+                            (unsigned long long)prefix_blocks[i], (unsigned long long)(p->host[i].len / 64));
+        const int rc = plan_prefixes(p, prefix_blocks);
+        if (rc) return rc;
+    }
+    p->pfx_mode = mode;
     return RF_OK;
 }
 
@@ -728,6 +906,10 @@ extern "C" void rf_sha_plan_destroy(rf_sha_plan* p) {
     p->d_host_ids.release();
     p->d_host_dig.release();
     p->h_host_dig.release();
+    p->d_pfx_ids.release();
+    p->d_pfx_blocks.release();
+    p->d_pfx_slot.release();
+    if (p->hand) (void)hipHostFree(p->hand);
     delete p;
 }
 

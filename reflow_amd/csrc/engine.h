@@ -37,6 +37,20 @@ struct SoloArgs {
 };
 // duo: the round chain on two lanes (k1_sha256_duo); else one lane (k1_sha256_solo)
 hipError_t launch_sha_solo(const SoloArgs& a, bool duo, hipStream_t s);
+// Prefix hand-over (host_sched.h): entry j is the first blocks[j] whole blocks
+// of message ids[j]; its chaining value (eight state words, host order) goes to
+// mid[8 * slot[j] ..] and then ready[slot[j]] = 1.  mid and ready are the
+// device addresses of coherent pinned host memory the host leg polls once.
+struct PrefixArgs {
+    const uint32_t* ids;
+    const uint64_t* blocks;
+    const uint32_t* slot;
+    uint32_t n;
+    uint32_t* mid;
+    uint32_t* ready;
+};
+// One k1_sha256_duo launch: a's messages whole (digests), then pa's prefixes.
+hipError_t launch_sha_duo_prefix(const SoloArgs& a, const PrefixArgs& pa, hipStream_t s);
 // Lane per message with a producer wave beside the chain wave (small sets).
 hipError_t launch_sha_pair(const SoloArgs& a, hipStream_t s);
 // Eight messages per wave on the duo's two-lane chain (small sets).

@@ -144,11 +144,13 @@ int host_ways() {
 
 namespace {
 // One message in flight on a host thread.  Its bytes come in chunks of C
-// (from the message start, so every chunk but the last is whole blocks):
+// (from the message start, or from the end of a prefix taken over from the
+// GPU -- whole blocks either way -- so every chunk but the last is whole
+// blocks; len counts from there, total is the message's length):
 // from HBM through the lane's double buffer, or straight from host memory.
 struct Lane {
     bool active = false, ready = false;
-    uint64_t task = 0, len = 0, nch = 0, c = 0, pos = 0;
+    uint64_t task = 0, len = 0, total = 0, nch = 0, c = 0, pos = 0;
     int buf = 0;
     const uint8_t* src = nullptr;
     uint32_t st[8];
@@ -156,8 +158,9 @@ struct Lane {
 }  // namespace
 
 bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8_t* d_arena,
-                  const uint8_t* h_arena, uint8_t* out32, std::string* err) {
+                  const uint8_t* h_arena, uint8_t* out32, std::string* err, HostLegStats* stats) {
     std::atomic<uint64_t> next{0};
+    std::atomic<uint64_t> taken{0}, missed{0}, skipped{0};
     std::atomic<bool> bad{false};
     std::mutex emu;
     const bool timing = leg_timing();
@@ -194,11 +197,23 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
             x.active = false;
             for (uint64_t i; !bad.load(std::memory_order_relaxed) && (i = next.fetch_add(1)) < n;) {
                 x.task = i;
-                x.len = tasks[i].len;
-                x.src = (h_arena ? h_arena : d_arena) + tasks[i].off;
+                x.total = tasks[i].len;
                 host_sha_init(x.st);
-                if (!x.len) {
-                    host_sha_final(x.st, nullptr, 0, 0, out32 + 32 * i);
+                uint64_t base = 0;
+                if (tasks[i].prefix_blocks) {  // one look at the flag, never a wait
+                    if (__atomic_load_n(tasks[i].ready, __ATOMIC_ACQUIRE)) {
+                        memcpy(x.st, tasks[i].mid, 32);
+                        base = 64 * tasks[i].prefix_blocks;
+                        taken.fetch_add(1, std::memory_order_relaxed);
+                        skipped.fetch_add(base, std::memory_order_relaxed);
+                    } else {
+                        missed.fetch_add(1, std::memory_order_relaxed);
+                    }
+                }
+                x.len = x.total - base;
+                x.src = (h_arena ? h_arena : d_arena) + tasks[i].off + base;
+                if (!x.len) {  // empty, or the prefix was every byte: padding only
+                    host_sha_final(x.st, nullptr, 0, x.total, out32 + 32 * i);
                     continue;
                 }
                 x.nch = (x.len + C - 1) / C;
@@ -255,7 +270,7 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                     x.buf ^= 1;
                     x.ready = h_arena != nullptr;
                 } else {  // the tail: pad, finish, take the next message
-                    host_sha_final(x.st, data(x, idx[a]) + x.pos, cl - x.pos, x.len, out32 + 32 * x.task);
+                    host_sha_final(x.st, data(x, idx[a]) + x.pos, cl - x.pos, x.total, out32 + 32 * x.task);
                     claim(idx[a]);
                 }
             }
@@ -263,6 +278,11 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
         }
         if (timing) tt[w] = now_s() - t_start;
     });
+    if (stats) {
+        stats->taken = taken.load();
+        stats->missed = missed.load();
+        stats->skipped_bytes = skipped.load();
+    }
     if (timing) {
         double sw = 0, sh = 0, mx = 0;
         for (unsigned w = 0; w < pool.size(); ++w) {
@@ -272,10 +292,13 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
         }
         uint64_t bytes = 0;
         for (uint64_t i = 0; i < n; ++i) bytes += tasks[i].len;
+        bytes -= skipped.load();  // what the threads hashed
         fprintf(stderr, "[host leg] %u threads x %d ways, %llu msgs, %.2f GB: wall %.1f ms, slowest thread %.1f ms; "
-                        "sum wait %.1f ms, sum hash %.1f ms (%.2f GB/s per hashing thread)\n",
+                        "sum wait %.1f ms, sum hash %.1f ms (%.2f GB/s per hashing thread); prefixes taken %llu, "
+                        "missed %llu, %.3f GB skipped\n",
                 pool.size(), W, (unsigned long long)n, bytes / 1e9, (now_s() - t_run) * 1e3, mx * 1e3, sw * 1e3,
-                sh * 1e3, sh > 0 ? bytes / sh / 1e9 : 0.0);
+                sh * 1e3, sh > 0 ? bytes / sh / 1e9 : 0.0, (unsigned long long)taken.load(),
+                (unsigned long long)missed.load(), skipped.load() / 1e9);
     }
     return !bad.load();
 }

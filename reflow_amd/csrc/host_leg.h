@@ -77,6 +77,21 @@ struct HostTask {
     uint32_t id;    // message id (row of the plan's out32)
     uint64_t off;   // byte offset in the arena
     uint64_t len;
+    // Prefix hand-over (host_sched.h): a GPU wave hashes the first
+    // prefix_blocks whole blocks meanwhile and then writes the chaining value
+    // (eight words, host order) to mid and 1 to *ready.  The thread that
+    // claims the task looks at *ready ONCE: set, it resumes from mid at byte
+    // 64 * prefix_blocks; unset, it hashes the whole message.  It never waits,
+    // so a late or failed wave costs nothing but that wave.
+    uint64_t prefix_blocks = 0;
+    const uint32_t* mid = nullptr;
+    const uint32_t* ready = nullptr;
+};
+
+// Prefixes of one host_leg_run: found ready, found not ready, and the bytes
+// the host did not hash (64 x the taken prefixes' blocks).
+struct HostLegStats {
+    uint64_t taken = 0, missed = 0, skipped_bytes = 0;
 };
 
 // Messages one host thread hashes at once, interleaved (host_sha_blocks_multi):
@@ -90,7 +105,7 @@ int host_ways();
 // chunked D2H; the caller has waited until its bytes are written) and h_arena
 // (host memory) is non-null.  Returns false with *err set on a HIP failure.
 bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8_t* d_arena,
-                  const uint8_t* h_arena, uint8_t* out32, std::string* err);
+                  const uint8_t* h_arena, uint8_t* out32, std::string* err, HostLegStats* stats = nullptr);
 
 // Streaming absorb with a carry block: feeds len bytes at p into midstate st
 // whose pending partial block is carry[0 .. *carry_len).

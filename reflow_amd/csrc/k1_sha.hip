@@ -267,7 +267,14 @@ __global__ __launch_bounds__(64) void k1_sha256_solo(SoloArgs a) {
 // Two waves: wave 0 runs the chain, wave 1 expands the next 64 blocks'
 // K+W rows into the other half of a double buffer meanwhile (one barrier per
 // 64 blocks), so the chain never waits for HBM or the message schedule.
-__global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a) {
+//
+// kPrefix: the launch also carries prefix hand-overs (PrefixArgs, engine.h):
+// workgroups q >= a.n_order hash only the first pa.blocks[j] whole blocks of
+// their message -- the producer still sees the real length, so no padding
+// appears -- and leave the chaining value and a ready flag in host memory
+// for the host leg, which resumes from there (host_leg.h).
+template <bool kPrefix>
+__global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) {
     // two buffers of 64 K+W rows, then the a-lanes' k row: word 0 = 0
     // (block-start add), the rest 1 (Zt = -c)
     __shared__ __attribute__((aligned(16))) uint32_t kw[129 * kRow];
@@ -289,11 +296,13 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a) {
     const uint32_t shq = elane ? (q3 == 1 ? 11u : q3 == 2 ? 25u : 6u) : (q3 == 1 ? 13u : q3 == 2 ? 22u : 2u);
     const uint32_t M = elane ? 0u : ~0u;
     const uint32_t one = 1u, zero = 0u;
-    for (uint32_t q = blockIdx.x; q < a.n_order; q += gridDim.x) {
-        const uint32_t id = a.order[q];
+    const uint32_t n_wg = kPrefix ? a.n_order + pa.n : a.n_order;
+    for (uint32_t q = blockIdx.x; q < n_wg; q += gridDim.x) {
+        const bool pfx = kPrefix && q >= a.n_order;  // uniform over the workgroup
+        const uint32_t id = pfx ? pa.ids[q - a.n_order] : a.order[q];
         const uint8_t* p = a.arena + a.offs[id];
         const uint64_t len = a.lens[id];
-        const uint64_t nb = sha256_nblocks(len);
+        const uint64_t nb = pfx ? pa.blocks[q - a.n_order] : sha256_nblocks(len);
         // Start as if after a block whose raw final state is zero with
         // chaining value IV: the feed-forward of block 0's group 0 then
         // produces the IV state and the corrections below are the general
@@ -369,6 +378,16 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a) {
                      : RF_LAG_STATE, RF_LAG_TMP, RF_LAG_H
                      : RF_LAG_IN(one, one, one, one));
         // lane 8 (a-lane) holds H0..H3, lane 0 (e-lane) H4..H7
+        if (kPrefix && pfx) {
+            // the chaining value as it is (no byte swap), then the flag: the
+            // host takes the value only after it has seen the flag
+            const uint32_t sl = pa.slot[q - a.n_order];
+            if (lane == 0 || lane == 8)
+                reinterpret_cast<uint4*>(pa.mid + 8ull * sl)[lane == 0 ? 1 : 0] = make_uint4(Hr0, Hr1, Hr2, Hr3);
+            __threadfence_system();
+            if (lane == 0) __hip_atomic_store(pa.ready + sl, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+        }
         if (lane == 0 || lane == 8) {
             uint4 o;
             o.x = bswap32(Hr0); o.y = bswap32(Hr1); o.z = bswap32(Hr2); o.w = bswap32(Hr3);
@@ -678,9 +697,15 @@ hipError_t launch_sha_lanes(const LanesArgs& a, uint32_t grid, hipStream_t s) {
 hipError_t launch_sha_solo(const SoloArgs& a, bool duo, hipStream_t s) {
     if (a.n_order == 0) return hipSuccess;
     if (duo)
-        hipLaunchKernelGGL(k1_sha256_duo, dim3(a.n_order), dim3(128), 0, s, a);
+        hipLaunchKernelGGL(k1_sha256_duo<false>, dim3(a.n_order), dim3(128), 0, s, a, PrefixArgs{});
     else
         hipLaunchKernelGGL(k1_sha256_solo, dim3(a.n_order), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sha_duo_prefix(const SoloArgs& a, const PrefixArgs& pa, hipStream_t s) {
+    if (a.n_order + pa.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k1_sha256_duo<true>, dim3(a.n_order + pa.n), dim3(128), 0, s, a, pa);
     return hipGetLastError();
 }
 
