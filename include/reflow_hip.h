@@ -451,6 +451,81 @@ typedef struct {
  * this one). */
 int rf_graph_stats_get(rf_graph *g, rf_graph_stats *out);
 
+/* ---- Change feed: the cache keys a step changed, found on the device ------
+ * After a step an incremental evaluator looks up again only the nodes whose
+ * cache keys moved (Flow.CacheKeys, flow.go:796-802, then Eval.lookup's
+ * Assoc.Get, eval.go:1172-1220).  An opt-in feed on a loaded graph reports
+ * the job-output slots whose digests changed since the last poll, ascending,
+ * with their new digests -- on the device, asynchronously on a stream, after
+ * one plain incremental step with work proportional to the dirty set -- and a
+ * fused lookup runs those keys through the liveset probe and the HBM assoc in
+ * the same stream.  One feed per graph, owned by it: rf_graph_destroy frees
+ * it.  A graph without a feed launches exactly what it launched before.
+ * Footprint: 32 B a slot (the digests as last reported) + 2 bits a slot (mask
+ * and pending bitmaps, padded to 8192 slots) + 4 B per input slot marked
+ * between two polls.
+ *
+ * open: the graph must be recomputed with no change set pending and no
+ * partition attached (RF_EPRECONDITION otherwise, as for a second open;
+ * rf_graph_set_part on a graph with a feed is RF_EPRECONDITION too).  The
+ * baseline is the slot table as it stands (steps queued on any stream
+ * complete first).  mask_words: [ceil(n_slots / 64)], bit s (bit s % 64 of
+ * word s / 64) = report slot s; NULL = every job-output slot.  Input slots
+ * are never reported (the caller set them): a mask bit on one, or at or
+ * beyond n_slots, is RF_EINVAL.
+ *
+ * poll: every tracked slot whose digest differs from what the feed last
+ * reported for it (or from the baseline), strictly ascending, each with its
+ * current digest.  Digests are compared, history is not replayed: a slot that
+ * changed and changed back between polls is not reported; one that changed
+ * twice is reported once, with the latest digest.  *found = the number of
+ * such slots, *written = min(found, cap); the first `written` in ascending
+ * order are written, the rest stay pending and lead the next poll (nothing is
+ * ever lost; cap = 0 is a count, slots / digests32 may then be NULL).  The
+ * host form returns RF_OK whether they all fit or not.  The device form is
+ * asynchronous on `stream` (d_n2: u64 {found, written}); the caller orders it
+ * after the step, on the same stream or otherwise, as everywhere in this ABI.
+ * Modes (rf_graph_feed_stats.last_mode): RF_FEED_LISTED when since the
+ * previous poll (or the open) input slots were set any number of times and
+ * then exactly one plain incremental step ran -- rf_graph_recompute(_async)
+ * with full = 0 or rf_graph_update_recompute_async -- and nothing wrote slots
+ * after it: the poll compares that step's listed jobs, the slot-fused jobs of
+ * the slots marked for it, and their fused chains; also when nothing happened
+ * at all (only what earlier polls left pending).  RF_FEED_SCAN otherwise (two
+ * steps, a full recompute, rf_graph_adopt_slots, a captured-graph step, slots
+ * set after the step or not stepped yet) and with RF_FEED_FORCE_SCAN: every
+ * tracked slot is compared.  The results are identical.
+ *
+ * lookup: the poll, then for every written key i: status[i] = 2 when `live`
+ * (may be NULL: no liveset) does not contain it -- the assoc is not read,
+ * vals32[i] zeroed; 1 = found in `a` under `kind`, vals32[i] the value; 0 =
+ * NotExist, vals32[i] zeroed: what rf_graph_feed_poll + rf_bloom_probe +
+ * rf_assoc_get give composed on the host.  Rows at and beyond `written` are
+ * not touched.  g, live and a must share one context (RF_EINVAL).  A later
+ * growth or compaction of `a` waits for the queued read, as for
+ * rf_assoc_get_device.
+ *
+ * rf_graph_save ignores the feed; a restored graph has none. */
+#define RF_FEED_FORCE_SCAN 1u /* poll flag: test / A-B control, see modes */
+enum { RF_FEED_NONE = 0, RF_FEED_LISTED = 1, RF_FEED_SCAN = 2 };
+typedef struct {
+    uint64_t polls, polls_listed, polls_scan;
+    uint32_t last_mode;     /* RF_FEED_* of the last poll */
+    uint64_t tracked_slots; /* job-output slots under the mask */
+    uint64_t device_bytes;  /* what the feed holds in HBM */
+} rf_graph_feed_stats;
+int rf_graph_feed_open(rf_graph *g, const uint64_t *mask_words);
+int rf_graph_feed_close(rf_graph *g);
+int rf_graph_feed_poll_device(rf_graph *g, uint32_t flags, uint64_t cap, void *d_slots /* u32[cap] */,
+                              void *d_digests32 /* [cap][32] */, void *d_n2 /* u64[2]: found, written */,
+                              void *stream);
+int rf_graph_feed_poll(rf_graph *g, uint32_t flags, uint64_t cap, uint32_t *slots, uint8_t *digests32,
+                       uint64_t *found, uint64_t *written);
+int rf_graph_feed_lookup_device(rf_graph *g, rf_bloom *live /* may be NULL */, rf_assoc *a, int kind, uint32_t flags,
+                                uint64_t cap, void *d_slots, void *d_keys32, void *d_status /* u8[cap] */,
+                                void *d_vals32, void *d_n2, void *stream);
+int rf_graph_feed_stats_get(rf_graph *g, rf_graph_feed_stats *out);
+
 /* ---- Checkpoint / resume of a loaded DAG ------------------------
  * Reference: a run's State is marshalled after every runner step
  * (runner/runner.go:51-85) and the local executor restores its execs from

@@ -448,6 +448,9 @@ Flow* Canonicalize(Engine& e, FlowArena& arena, Flow* root, Config config,
 // OpExec/OpExtern whose deps are Done) and evaluated on the device.  With
 // file_slots, every File.ID inside Fileset values becomes an input slot, so
 // SetFileID + Recompute re-derive only the dependents (incremental).
+class Liveset;
+class Assoc;
+enum AssocKind : int;
 class Eval {
    public:
     Eval(Engine& e, std::string universe = "", bool file_slots = false);
@@ -462,6 +465,31 @@ class Eval {
     uint64_t Recompute(bool full = false);
     size_t Jobs() const { return out_slot_.size(); }
     size_t Collapsed() const { return collapsed_; }  // copies Canonicalize collapsed into a first copy
+    // The change feed (rf_graph_feed_*): which job-output slots -- digests and
+    // cache keys, flow.go:796-802 -- the steps since the last poll moved, found
+    // on the device; only those nodes need a new Eval.lookup (eval.go:1172-1220).
+    // mask_words: [ceil(slots / 64)], bit s = report slot s; null: every one.
+    struct Changed {
+        uint32_t slot;
+        Digest digest;
+    };
+    void FeedOpen(const std::vector<uint64_t>* mask_words = nullptr);
+    void FeedClose();
+    // At most cap changed slots, ascending (the rest lead the next poll);
+    // *found: how many there were.
+    std::vector<Changed> FeedPoll(uint64_t cap = UINT64_MAX, bool force_scan = false, uint64_t* found = nullptr);
+    // The poll fused with the liveset probe and the assoc Get on the device
+    // (rf_graph_feed_lookup_device): status 2 = not in `live` (may be null),
+    // 1 = found (value set), 0 = NotExist.
+    struct Looked {
+        uint32_t slot;
+        Digest key;
+        int status;
+        Digest value;
+    };
+    std::vector<Looked> FeedLookup(Liveset* live, Assoc& a, AssocKind kind, uint64_t cap = UINT64_MAX,
+                                   uint64_t* found = nullptr);
+    rf_graph_feed_stats FeedStats() const;
 
    private:
     friend Flow* Canonicalize(Engine&, FlowArena&, Flow*, Config, const std::string&, std::unique_ptr<Eval>*);
@@ -538,6 +566,7 @@ class Liveset {
                                                       const std::vector<int64_t>& sizes);
 
    private:
+    friend class Eval;  // (FeedLookup)
     explicit Liveset(rf_bloom* b) : b_(b) {}
     rf_bloom* b_ = nullptr;
 };
@@ -589,6 +618,7 @@ class Assoc {
     std::pair<uint64_t, uint64_t> Stats();  // (occupied, capacity)
 
    private:
+    friend class Eval;  // (FeedLookup)
     Assoc() = default;
     rf_assoc* a_ = nullptr;
 };

@@ -24,6 +24,10 @@ RF_SHA_ALL_HOST = 32
 RF_SHA_NO_HOST = 64
 RF_SHA_NO_PREFIX = 128
 RF_PREFIX_RACE, RF_PREFIX_WAIT, RF_PREFIX_MISS = 0, 1, 2
+# change feed (rf_graph_feed_*): poll flag, poll modes, slots per compaction tile
+RF_FEED_FORCE_SCAN = 1
+RF_FEED_NONE, RF_FEED_LISTED, RF_FEED_SCAN = 0, 1, 2
+FEED_TILE_SLOTS = 8192
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -58,6 +62,8 @@ EXPORTS = [
     "rf_coalescer_stats", "rf_graph_update_recompute_async", "rf_walk_dir", "rf_walk_info", "rf_walk_entries", "rf_walk_free",
     "rf_graph_set_part", "rf_graph_recompute_part", "rf_graph_part_gathered", "rf_graph_split",
     "rf_graph_piece_free", "rf_graph_piece_desc", "rf_graph_piece_part", "rf_graph_piece_slots",
+    "rf_graph_feed_open", "rf_graph_feed_close", "rf_graph_feed_poll", "rf_graph_feed_poll_device",
+    "rf_graph_feed_lookup_device", "rf_graph_feed_stats_get",
 ]
 
 
@@ -247,6 +253,12 @@ class GraphStats(ctypes.Structure):
                 ("last_sink_attach", ctypes.c_uint32), ("last_levels_half", ctypes.c_uint32)]
 
 
+class GraphFeedStats(ctypes.Structure):
+    _fields_ = [("polls", ctypes.c_uint64), ("polls_listed", ctypes.c_uint64), ("polls_scan", ctypes.c_uint64),
+                ("last_mode", ctypes.c_uint32), ("tracked_slots", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -388,6 +400,11 @@ def lib():
             "rf_graph_update_recompute_async": ([vp, vp, vp, u32, vp], i32),
             "rf_walk_dir": ([ctypes.c_char_p, vp], i32), "rf_walk_info": ([vp, vp, vp], i32),
             "rf_walk_entries": ([vp, vp, vp, vp], i32), "rf_walk_free": ([vp], None),
+            "rf_graph_feed_open": ([vp, vp], i32), "rf_graph_feed_close": ([vp], i32),
+            "rf_graph_feed_poll": ([vp, u32, u64, vp, vp, vp, vp], i32),
+            "rf_graph_feed_poll_device": ([vp, u32, u64, vp, vp, vp, vp], i32),
+            "rf_graph_feed_lookup_device": ([vp, vp, vp, i32, u32, u64, vp, vp, vp, vp, vp, vp], i32),
+            "rf_graph_feed_stats_get": ([vp, vp], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -918,6 +935,49 @@ class Graph:
         p, n, st = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().rf_graph_part_gathered(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(st)))
         return p.value, n.value, st.value
+
+    # ---- change feed (include/reflow_hip.h "Change feed") ----
+    def feed_open(self, mask=None):
+        """rf_graph_feed_open.  mask: None (every job-output slot), a uint64
+        word array [ceil(n_slots / 64)], or a bool array over the slots."""
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype == np.bool_:
+                bits = np.zeros((len(mask) + 63) // 64 * 64, dtype=np.uint8)
+                bits[:len(mask)] = mask
+                mask = np.packbits(bits, bitorder="little").view("<u8")
+            mask = np.ascontiguousarray(mask, dtype=np.uint64)
+        _check(lib().rf_graph_feed_open(self._h, _ptr(mask) if mask is not None and len(mask) else None))
+
+    def feed_close(self):
+        _check(lib().rf_graph_feed_close(self._h))
+
+    def feed_poll(self, cap=None, flags=0):
+        """rf_graph_feed_poll: (slots uint32[written], digests uint8[written][32],
+        found).  cap None: room for every tracked slot."""
+        if cap is None:
+            cap = self.feed_stats().tracked_slots
+        cap = int(cap)
+        slots = np.zeros(max(cap, 1), dtype=np.uint32)
+        dig = np.zeros((max(cap, 1), 32), dtype=np.uint8)
+        found, written = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().rf_graph_feed_poll(self._h, flags, cap, _ptr(slots), _ptr(dig), ctypes.byref(found),
+                                        ctypes.byref(written)))
+        return slots[:written.value].copy(), dig[:written.value].copy(), found.value
+
+    def feed_poll_device(self, cap, d_slots, d_digests32, d_n2, flags=0, stream=None):
+        _check(lib().rf_graph_feed_poll_device(self._h, flags, cap, d_slots, d_digests32, d_n2, stream))
+
+    def feed_lookup_device(self, live, assoc, kind, cap, d_slots, d_keys32, d_status, d_vals32, d_n2, flags=0,
+                           stream=None):
+        """rf_graph_feed_lookup_device: live a Bloom or None, assoc an Assoc."""
+        _check(lib().rf_graph_feed_lookup_device(self._h, live._h if live is not None else None, assoc._h, kind,
+                                                 flags, cap, d_slots, d_keys32, d_status, d_vals32, d_n2, stream))
+
+    def feed_stats(self) -> GraphFeedStats:
+        s = GraphFeedStats()
+        _check(lib().rf_graph_feed_stats_get(self._h, ctypes.byref(s)))
+        return s
 
     def close(self):
         if self._h:

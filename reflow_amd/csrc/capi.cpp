@@ -1900,6 +1900,12 @@ extern "C" int rf_graph_load(rf_ctx* ctx, const rf_graph_desc* d, rf_graph** out
     return RF_OK;
 }
 
+// The change feed's hooks (defined with rf_graph_feed_* below; no-ops on a
+// graph without a feed -- gr->feed is null and nothing is launched).
+static int feed_on_mark(rf_graph* gr, const uint32_t* d_slots, uint32_t n, hipStream_t s);
+static void feed_on_step(rf_graph* gr, bool full, bool whole_plain);
+static void feed_on_write(rf_graph* gr);
+
 extern "C" void rf_graph_destroy(rf_graph* gr) {
     if (!gr) return;
     if (gr->ctx) {
@@ -1915,6 +1921,7 @@ extern "C" void rf_graph_destroy(rf_graph* gr) {
         if (gr->graph_upd) (void)hipGraphDestroy(gr->graph_upd);
         if (gr->exec_full) (void)hipGraphExecDestroy(gr->exec_full);
         graph_part_release(gr);
+        graph_feed_release(gr);
     }
     delete gr;
 }
@@ -1974,6 +1981,8 @@ extern "C" int rf_graph_set_slots(rf_graph* gr, const uint32_t* slots, const uin
     } else {
         HIPC(launch_graph_mark_slots(gr->g, gr->b_tmp_idx.as<uint32_t>(), gr->b_tmp_dig.as<uint8_t>(), n,
                                      ctx->stream));
+        if (gr->feed)
+            if (int rc = feed_on_mark(gr, gr->b_tmp_idx.as<uint32_t>(), n, ctx->stream)) return rc;
     }
     HIPC(hipStreamSynchronize(ctx->stream));
     lap("mark");
@@ -1992,6 +2001,8 @@ extern "C" int rf_graph_set_slots_device(rf_graph* gr, const void* d_slots, cons
     } else {
         HIPC(launch_graph_mark_slots(gr->g, static_cast<const uint32_t*>(d_slots),
                                      static_cast<const uint8_t*>(d_digests32), n, pick(gr->ctx, stream)));
+        if (gr->feed && n)
+            if (int rc = feed_on_mark(gr, static_cast<const uint32_t*>(d_slots), n, pick(gr->ctx, stream))) return rc;
     }
     gr->marked += n;
     return RF_OK;
@@ -2070,6 +2081,7 @@ extern "C" int rf_graph_adopt_slots(rf_graph* gr, rf_graph* src) {
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     gr->initialized = true;
+    if (gr->feed) feed_on_write(gr);
     return RF_OK;
 }
 
@@ -2249,6 +2261,7 @@ int graph_recompute_locked(rf_graph* gr, int full, hipStream_t s, uint32_t lvl_l
         if (ev) HIPC(hipEventRecord(gr->e1, s));
         gr->timed = ev;
         gr->initialized = true;
+        if (gr->feed) feed_on_step(gr, full != 0, lvl_lo == 0 && lvl_hi == ~0u && swap);
         return RF_OK;
     }
     hipGraphExec_t& ex = full ? gr->exec_full : gr->exec_inc;
@@ -2261,6 +2274,7 @@ int graph_recompute_locked(rf_graph* gr, int full, hipStream_t s, uint32_t lvl_l
     HIPC(hipEventRecord(gr->e1, s));
     gr->timed = true;
     gr->initialized = true;
+    if (gr->feed) feed_on_step(gr, full != 0, false);  // (a captured step: its lists are gone at its end)
     return RF_OK;
 }
 
@@ -2316,6 +2330,8 @@ extern "C" int rf_graph_update_recompute_async(rf_graph* gr, const void* d_slots
     if (!gr->initialized || inc_plain()) {  // mark, then the level launches (first call: the full sequence)
         HIPC(launch_graph_mark_slots(gr->g, static_cast<const uint32_t*>(d_slots),
                                      static_cast<const uint8_t*>(d_digests32), n, s));
+        if (gr->feed && gr->initialized && n)
+            if (int rc = feed_on_mark(gr, static_cast<const uint32_t*>(d_slots), n, s)) return rc;
         gr->marked += n;
         return graph_recompute_locked(gr, gr->initialized ? 0 : 1, s);
     }
@@ -2332,6 +2348,7 @@ extern "C" int rf_graph_update_recompute_async(rf_graph* gr, const void* d_slots
     HIPC(hipGraphLaunch(gr->exec_upd, s));
     HIPC(hipEventRecord(gr->e1, s));
     gr->timed = true;
+    if (gr->feed) feed_on_write(gr);
     return RF_OK;
 }
 
@@ -3369,5 +3386,239 @@ extern "C" int rf_assoc_restore(rf_ctx* ctx, const char* path, rf_assoc** out) {
     HIPC(hipStreamSynchronize(s));
     guard.release();
     *out = a;
+    return RF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Graph change feed (rf_graph_feed_*): the job-output slots whose digests
+// moved since the last poll, found on the device (k6_feed.hip); which way a
+// poll looks for them is feed_state.h's decision, fed by the hooks below.
+void graph_feed_release(rf_graph* gr) {
+    GraphFeed* F = gr->feed;
+    if (!F) return;
+    for (DevBuf* b : {&F->b_shadow, &F->b_mask, &F->b_pending, &F->b_tiles, &F->b_sf, &F->b_slots, &F->b_dig, &F->b_n2})
+        b->release();
+    delete F;
+    gr->feed = nullptr;
+}
+
+// Input slots were marked on the recomputed graph (the mark kernel is queued
+// on s): their slot-fused jobs, which the mark kernel hashes at once and
+// never lists, join the next LISTED poll's candidates.
+static int feed_on_mark(rf_graph* gr, const uint32_t* d_slots, uint32_t n, hipStream_t s) {
+    GraphFeed& F = *gr->feed;
+    if (!gr->g.plan) {  // (the A/B build without the per-slot plan: scan)
+        feed_apply(F.st, kFeedOtherWrite);
+        return RF_OK;
+    }
+    if (feed_records_marks(F.st)) {
+        const uint64_t need = 4ull * (F.sf_n + n);
+        if (need > F.b_sf.cap) {  // grow: the recorded ids move to a buffer twice the size
+            DevBuf nb;
+            HIPC(nb.ensure(std::max<uint64_t>(2 * need, 1u << 18)));
+            hipError_t e = hipSuccess;
+            if (F.sf_n) {
+                e = hipMemcpyAsync(nb.p, F.b_sf.p, 4ull * F.sf_n, hipMemcpyDeviceToDevice, s);
+                if (e == hipSuccess) e = hipStreamSynchronize(s);
+            }
+            if (e != hipSuccess) {
+                nb.release();
+                return fail(RF_EDEVICE, "feed: growing the mark record: %s", hipGetErrorString(e));
+            }
+            F.b_sf.release();
+            F.b_sf = nb;
+        }
+        HIPC(launch_feed_record(gr->g, d_slots, n, F.b_sf.as<uint32_t>() + F.sf_n, s));
+        F.sf_n += n;
+    }
+    feed_apply(F.st, kFeedSetSlots);
+    return RF_OK;
+}
+
+// A recompute was queued: full, one whole plain incremental step (its lists
+// stay in the cursor half gr->last_counts until the next step's marks), or
+// anything else (a captured step, part of a step).
+static void feed_on_step(rf_graph* gr, bool full, bool whole_plain) {
+    GraphFeed& F = *gr->feed;
+    if (full) {
+        feed_apply(F.st, kFeedFull);
+    } else if (whole_plain) {
+        feed_apply(F.st, kFeedPlainStep);
+        // (a graph with no queueable level ran the captured sequence: nothing was listed)
+        if (F.st.phase == kFeedStepped) F.lists = gr->last_counts != gr->g.counts_last ? gr->last_counts : nullptr;
+    } else {
+        feed_apply(F.st, kFeedOtherWrite);
+    }
+}
+
+static void feed_on_write(rf_graph* gr) { feed_apply(gr->feed->st, kFeedOtherWrite); }
+
+extern "C" int rf_graph_feed_open(rf_graph* gr, const uint64_t* mask_words) {
+    ARG(gr, "null graph");
+    rf_ctx* ctx = gr->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (gr->feed) return fail(RF_EPRECONDITION, "feed_open: the graph already has a feed");
+    if (!gr->initialized) return fail(RF_EPRECONDITION, "feed_open: the graph was never recomputed");
+    if (gr->marked) return fail(RF_EPRECONDITION, "feed_open: input slots set since the last recompute");
+    if (gr->part) return fail(RF_EPRECONDITION, "feed_open: the graph is a piece of a partition");
+    const uint64_t S = gr->g.n_slots, nw64 = (S + 63) / 64;
+    uint64_t tracked = 0;
+    if (mask_words) {
+        for (uint64_t i = 0; i < nw64; ++i)
+            for (uint64_t q = mask_words[i]; q; q &= q - 1) {
+                const uint64_t s = 64 * i + (uint64_t)__builtin_ctzll(q);
+                if (s >= S) return fail(RF_EINVAL, "feed_open: mask bit %llu beyond the %llu slots", (unsigned long long)s, (unsigned long long)S);
+                if (gr->producer[s] < 0) return fail(RF_EINVAL, "feed_open: mask bit on input slot %llu", (unsigned long long)s);
+                ++tracked;
+            }
+    } else {
+        for (uint64_t s = 0; s < S; ++s) tracked += gr->producer[s] >= 0;
+    }
+    GraphFeed* F = gr->feed = new GraphFeed();
+    struct Undo {  // a failure below leaves the graph without a feed
+        rf_graph* gr;
+        bool keep = false;
+        ~Undo() {
+            if (!keep) graph_feed_release(gr);
+        }
+    } undo{gr};
+    F->tracked = tracked;
+    F->d.tiles = (uint32_t)std::max<uint64_t>(1, (S + kFeedTileSlots - 1) / kFeedTileSlots);
+    F->d.words = (uint64_t)F->d.tiles * (kFeedTileSlots / 32);
+    HIPC(F->b_shadow.ensure(32ull * std::max<uint64_t>(S, 1)));
+    HIPC(F->b_mask.ensure(4ull * F->d.words));
+    HIPC(F->b_pending.ensure(4ull * F->d.words));
+    HIPC(F->b_tiles.ensure(4ull * F->d.tiles));
+    HIPC(F->b_n2.ensure(16));
+    F->d.shadow = F->b_shadow.as<uint8_t>();
+    F->d.mask = F->b_mask.as<uint32_t>();
+    F->d.pending = F->b_pending.as<uint32_t>();
+    F->d.tile_count = F->b_tiles.as<uint32_t>();
+    // the baseline: the table as every step queued so far leaves it
+    HIPC(hipDeviceSynchronize());
+    if (S) HIPC(hipMemcpyAsync(F->d.shadow, gr->g.slots, 32ull * S, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(hipMemsetAsync(F->d.mask, 0, 4ull * F->d.words, ctx->stream));
+    HIPC(hipMemsetAsync(F->d.pending, 0, 4ull * F->d.words, ctx->stream));
+    const uint32_t* want = nullptr;
+    if (mask_words) {  // (little-endian: the caller's u64 words are the bitmap's u32 words in order)
+        HIPC(F->b_dig.ensure(4ull * F->d.words));
+        HIPC(hipMemsetAsync(F->b_dig.p, 0, 4ull * F->d.words, ctx->stream));
+        if (nw64) HIPC(hipMemcpyAsync(F->b_dig.p, mask_words, 8ull * nw64, hipMemcpyHostToDevice, ctx->stream));
+        want = F->b_dig.as<uint32_t>();
+    }
+    HIPC(launch_feed_mask(gr->g, F->d, want, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    feed_apply(F->st, kFeedOpen);
+    undo.keep = true;
+    return RF_OK;
+}
+
+extern "C" int rf_graph_feed_close(rf_graph* gr) {
+    ARG(gr, "null graph");
+    std::lock_guard<std::mutex> lk(gr->ctx->mu);
+    DevGuard dg(gr->ctx->device);
+    if (!gr->feed) return fail(RF_EPRECONDITION, "feed_close: the graph has no feed");
+    graph_feed_release(gr);
+    return RF_OK;
+}
+
+// One poll queued on s (context mutex held, feed open).
+static int feed_poll_locked(rf_graph* gr, uint32_t flags, uint64_t cap, uint32_t* d_slots, uint8_t* d_dig,
+                            uint64_t* d_n2, hipStream_t s) {
+    GraphFeed& F = *gr->feed;
+    const FeedPlan plan = feed_next_mode(F.st, (flags & RF_FEED_FORCE_SCAN) != 0);
+    if (plan.mode == kFeedScan)
+        HIPC(launch_feed_scan(gr->g, F.d, s));
+    else if (plan.candidates)
+        HIPC(launch_feed_listed(gr->g, F.d, F.lists, F.b_sf.as<uint32_t>(), F.sf_n, s));
+    HIPC(launch_feed_compact(gr->g, F.d, cap, d_slots, d_dig, d_n2, s));
+    feed_apply(F.st, kFeedPoll);
+    F.sf_n = 0;
+    F.lists = nullptr;
+    ++F.polls;
+    ++(plan.mode == kFeedScan ? F.polls_scan : F.polls_listed);
+    F.last_mode = plan.mode;
+    return RF_OK;
+}
+
+extern "C" int rf_graph_feed_poll_device(rf_graph* gr, uint32_t flags, uint64_t cap, void* d_slots, void* d_digests32,
+                                         void* d_n2, void* stream) {
+    ARG(gr && d_n2 && (cap == 0 || (d_slots && d_digests32)), "null argument");
+    ARG((flags & ~RF_FEED_FORCE_SCAN) == 0, "unknown poll flags");
+    std::lock_guard<std::mutex> lk(gr->ctx->mu);
+    DevGuard dg(gr->ctx->device);
+    if (!gr->feed) return fail(RF_EPRECONDITION, "feed_poll: the graph has no feed (rf_graph_feed_open)");
+    return feed_poll_locked(gr, flags, cap, static_cast<uint32_t*>(d_slots), static_cast<uint8_t*>(d_digests32),
+                            static_cast<uint64_t*>(d_n2), pick(gr->ctx, stream));
+}
+
+extern "C" int rf_graph_feed_poll(rf_graph* gr, uint32_t flags, uint64_t cap, uint32_t* slots, uint8_t* digests32,
+                                  uint64_t* found, uint64_t* written) {
+    ARG(gr && found && written && (cap == 0 || (slots && digests32)), "null argument");
+    ARG((flags & ~RF_FEED_FORCE_SCAN) == 0, "unknown poll flags");
+    rf_ctx* ctx = gr->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (!gr->feed) return fail(RF_EPRECONDITION, "feed_poll: the graph has no feed (rf_graph_feed_open)");
+    GraphFeed& F = *gr->feed;
+    const uint64_t ecap = std::min(cap, F.tracked);  // (found <= tracked: min(found, cap) is unchanged)
+    HIPC(F.b_slots.ensure(4ull * std::max<uint64_t>(ecap, 1)));
+    HIPC(F.b_dig.ensure(32ull * std::max<uint64_t>(ecap, 1)));
+    if (int rc = feed_poll_locked(gr, flags, ecap, F.b_slots.as<uint32_t>(), F.b_dig.as<uint8_t>(),
+                                  F.b_n2.as<uint64_t>(), ctx->stream))
+        return rc;
+    uint64_t n2[2] = {0, 0};
+    HIPC(hipMemcpyAsync(n2, F.b_n2.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (n2[1]) {
+        HIPC(hipMemcpyAsync(slots, F.b_slots.p, 4ull * n2[1], hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipMemcpyAsync(digests32, F.b_dig.p, 32ull * n2[1], hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));
+    }
+    *found = n2[0];
+    *written = n2[1];
+    return RF_OK;
+}
+
+extern "C" int rf_graph_feed_lookup_device(rf_graph* gr, rf_bloom* live, rf_assoc* a, int kind, uint32_t flags,
+                                           uint64_t cap, void* d_slots, void* d_keys32, void* d_status,
+                                           void* d_vals32, void* d_n2, void* stream) {
+    ARG(gr && a && d_n2 && (cap == 0 || (d_slots && d_keys32 && d_status && d_vals32)), "null argument");
+    ARG((flags & ~RF_FEED_FORCE_SCAN) == 0, "unknown poll flags");
+    ARG(kind >= 0 && kind < (1 << 30), "assoc kind out of range");
+    ARG(gr->ctx == a->ctx && (!live || live->ctx == gr->ctx), "graph, liveset and assoc of different contexts");
+    rf_ctx* ctx = gr->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);  // no Put may swap the table meanwhile
+    DevGuard dg(ctx->device);
+    if (!gr->feed) return fail(RF_EPRECONDITION, "feed_lookup: the graph has no feed (rf_graph_feed_open)");
+    hipStream_t s = pick(ctx, stream);
+    if (int rc = feed_poll_locked(gr, flags, cap, static_cast<uint32_t*>(d_slots), static_cast<uint8_t*>(d_keys32),
+                                  static_cast<uint64_t*>(d_n2), s))
+        return rc;
+    HIPC(launch_feed_lookup(live ? &live->b : nullptr, a->view(), (uint32_t)kind, static_cast<const uint8_t*>(d_keys32),
+                            static_cast<const uint64_t*>(d_n2), std::min(cap, gr->feed->tracked),
+                            static_cast<uint8_t*>(d_status), static_cast<uint8_t*>(d_vals32), s));
+    if (s != ctx->stream) {  // (as rf_assoc_get_device: growth and compaction wait for it)
+        if (!a->e_reader) HIPC(hipEventCreateWithFlags(&a->e_reader, hipEventDisableTiming));
+        HIPC(hipEventRecord(a->e_reader, s));
+        a->reader_pending = true;
+    }
+    return RF_OK;
+}
+
+extern "C" int rf_graph_feed_stats_get(rf_graph* gr, rf_graph_feed_stats* out) {
+    ARG(gr && out, "null argument");
+    std::lock_guard<std::mutex> lk(gr->ctx->mu);
+    if (!gr->feed) return fail(RF_EPRECONDITION, "feed_stats: the graph has no feed (rf_graph_feed_open)");
+    const GraphFeed& F = *gr->feed;
+    *out = rf_graph_feed_stats{};
+    out->polls = F.polls;
+    out->polls_listed = F.polls_listed;
+    out->polls_scan = F.polls_scan;
+    out->last_mode = F.last_mode;
+    out->tracked_slots = F.tracked;
+    for (const DevBuf* b : {&F.b_shadow, &F.b_mask, &F.b_pending, &F.b_tiles, &F.b_sf, &F.b_slots, &F.b_dig, &F.b_n2})
+        out->device_bytes += b->cap;
     return RF_OK;
 }

@@ -336,4 +336,38 @@ hipError_t launch_assoc_scan_count(const AssocView& t, uint32_t cap, int kind, v
 hipError_t launch_assoc_scan_scatter(const AssocView& t, uint32_t cap, const void* scratch, uint64_t cap_entries,
                                      void* keys_out, void* vals_out, void* kinds_out, hipStream_t s);
 
+// k4_collect_scan on its own: tile_count[tiles] becomes its exclusive scan in
+// place, *total (u64) the sum.
+hipError_t launch_tile_scan(uint32_t* tile_count, uint64_t tiles, uint64_t* total, hipStream_t s);
+
+// ---- K6: graph change feed (k6_feed.hip) --------------------------------------
+// Slots per compaction tile: one 256-lane workgroup of 32-slot bitmap words.
+constexpr uint32_t kFeedTileSlots = 8192;
+struct FeedDev {
+    uint8_t* shadow = nullptr;       // [S][32] the digests as last reported
+    uint32_t* mask = nullptr;        // [words] bit s: job output under the caller's mask
+    uint32_t* pending = nullptr;     // [words] bit s: differs from its shadow, not delivered yet
+    uint32_t* tile_count = nullptr;  // [tiles]
+    uint64_t words = 0;              // bitmap words: tiles * kFeedTileSlots / 32
+    uint32_t tiles = 0;              // max(1, ceil(S / kFeedTileSlots))
+};
+// f.mask (zeroed) |= want (u32 words as f.mask; null: every slot) & "is a job output"
+hipError_t launch_feed_mask(const GraphDev& g, const FeedDev& f, const uint32_t* want, hipStream_t s);
+// out[i] = the slot-fused job of input slot slots[i], or ~0u (g.plan)
+hipError_t launch_feed_record(const GraphDev& g, const uint32_t* slots, uint32_t n, uint32_t* out, hipStream_t s);
+// pending |= every slot under the mask that differs from its shadow
+hipError_t launch_feed_scan(const GraphDev& g, const FeedDev& f, hipStream_t s);
+// the same over the candidates of one plain step: its level lists (lists =
+// that step's cursor half; null: it listed nothing) and n_sf recorded
+// slot-fused jobs, each followed through its fusion targets
+hipError_t launch_feed_listed(const GraphDev& g, const FeedDev& f, const uint32_t* lists, const uint32_t* sf,
+                              uint64_t n_sf, hipStream_t s);
+// pending slots that still differ, ascending: n2 = {found, written = min(found,
+// cap)}; the first `written` delivered (slot, digest; shadow updated, bit cleared)
+hipError_t launch_feed_compact(const GraphDev& g, const FeedDev& f, uint64_t cap, uint32_t* out_slots,
+                               uint8_t* out_dig, uint64_t* n2, hipStream_t s);
+// keys[0 .. n2[1]) (at most max_n) through the liveset (null: none) and the assoc
+hipError_t launch_feed_lookup(const BloomDev* live, const AssocView& t, uint32_t kind, const uint8_t* keys,
+                              const uint64_t* n2, uint64_t max_n, uint8_t* status, uint8_t* vals, hipStream_t s);
+
 }  // namespace rf

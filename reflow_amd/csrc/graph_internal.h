@@ -6,6 +6,7 @@
 
 #include "ctx.h"
 #include "engine.h"
+#include "feed_state.h"
 
 // A loaded piece's place in a partitioned DAG (partition.cpp).
 struct GraphPart {
@@ -27,6 +28,20 @@ struct GraphPart {
     // above wait for the exchange (one hash of the import readers per step
     // instead of one before and one after it); ~0u: no deferral
     uint32_t defer_lvl = ~0u;
+};
+
+// The graph's change feed (rf_graph_feed_open; k6_feed.hip, feed_state.h).
+struct GraphFeed {
+    rf::FeedDev d;
+    rf::FeedState st;
+    DevBuf b_shadow, b_mask, b_pending, b_tiles;
+    DevBuf b_sf;          // slot-fused jobs of the input slots marked since the last poll
+    uint64_t sf_n = 0;    // entries of b_sf in use
+    const uint32_t* lists = nullptr;  // the one plain step's cursor half (null: it listed nothing)
+    DevBuf b_slots, b_dig, b_n2;      // the host-form poll's device outputs
+    uint64_t tracked = 0;
+    uint64_t polls = 0, polls_listed = 0, polls_scan = 0;
+    uint32_t last_mode = 0;
 };
 
 struct rf_graph {
@@ -56,6 +71,7 @@ struct rf_graph {
     uint64_t marked = 0;
     uint32_t* last_counts = nullptr;  // device cursors of the last recompute (counts_last, or a plain step's half)
     GraphPart* part = nullptr;  // multi-GPU partition (rf_graph_set_part), else null
+    GraphFeed* feed = nullptr;  // change feed (rf_graph_feed_open), else null
 };
 
 
@@ -70,3 +86,4 @@ uint32_t graph_ovf_cus(const rf_ctx* ctx, uint32_t* mode);  // RF_K2_OVF_CU / RF
 int graph_device_alloc(rf_graph* gr, uint32_t J, uint32_t S, uint32_t L, uint64_t H, uint64_t tmpl_bytes);
 int graph_build_plan(rf_graph* gr);  // GraphDev::plan, after the records are on the device
 void graph_part_release(rf_graph* gr);
+void graph_feed_release(rf_graph* gr);

@@ -17,28 +17,11 @@
 // hit), one 32-B compare read.  All of it is random access: the bound is the
 // random-gather rate, not HBM bandwidth.
 #include "engine.h"
+#include "assoc_dev.h"  // kEmpty, key_hash, key_eq, the tags, assoc_find
 
 namespace rf {
 
-constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr uint32_t kMaxProbe = 1u << 16;
-
-// 32-bit slot hash over all eight words of a 32-B key.  Each word enters
-// through an xor with a rotated partner and an odd multiply (bijections), so
-// two keys that differ in any single word never share a pre-finaliser value,
-// and the finaliser (also a bijection) spreads them over the low bits.  Keys
-// are usually SHA-256 output (any word would do), but callers may hand in
-// digests that share all but a few bytes.
-__device__ __forceinline__ uint32_t key_hash(const uint4& lo, const uint4& hi) {
-    uint32_t h = ((lo.x ^ __builtin_rotateleft32(lo.y, 5)) * 0x9E3779B1u) ^
-                 ((lo.z ^ __builtin_rotateleft32(lo.w, 11)) * 0x85EBCA77u) ^
-                 ((hi.x ^ __builtin_rotateleft32(hi.y, 17)) * 0xC2B2AE3Du) ^
-                 ((hi.z ^ __builtin_rotateleft32(hi.w, 23)) * 0x27D4EB2Fu);
-    h ^= h >> 16;
-    h *= 0x7FEB352Du;
-    h ^= h >> 15;
-    return h;
-}
 
 __device__ __forceinline__ bool dig_eq(const uint4& alo, const uint4& ahi, const uint8_t* b) {
     const uint4* q = reinterpret_cast<const uint4*>(b);
@@ -152,22 +135,12 @@ hipError_t launch_dedup(const uint8_t* dig, uint32_t n, uint32_t* table, uint32_
 // value; Put with a nonzero `expect` is a compare-and-set, a zero value
 // deletes.  Table: open addressing on key_hash(key), a tag word per
 // slot (0 empty, 1 being written, 2 + kind ready), keys and values 32 B each.
-// Deleted entries keep their slot with a zero value (Get: NotExist).
-constexpr uint32_t kTagEmpty = 0, kTagBusy = 1, kTagReady = 2;
-
-
 
 // Add a per-thread count to a global counter: one atomic per wave.  Called by
 // every lane of the wave after its grid-stride loop (converged).
 __device__ __forceinline__ void wave_count_add(uint32_t* counter, uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
-}
-
-__device__ __forceinline__ bool key_eq(const uint4* k, const uint4& lo, const uint4& hi) {
-    const uint4 a = k[0], b = k[1];
-    return ((a.x ^ lo.x) | (a.y ^ lo.y) | (a.z ^ lo.z) | (a.w ^ lo.w) | (b.x ^ hi.x) | (b.y ^ hi.y) |
-            (b.z ^ hi.z) | (b.w ^ hi.w)) == 0;
 }
 
 // Insert (or find) the batch's DISTINCT keys (canon[i] == i).  A slot is
@@ -221,17 +194,6 @@ __global__ __launch_bounds__(256) void k5_assoc_publish(AssocView t, uint32_t ki
             t.tag[so & 0x7fffffffu] = kTagReady + kind;
             slot_of[i] = so & 0x7fffffffu;
         }
-    }
-}
-
-__device__ __forceinline__ uint32_t assoc_find(const AssocView& t, uint32_t kind, const uint4& lo, const uint4& hi) {
-    const uint32_t ready = kTagReady + kind;
-    uint32_t slot = key_hash(lo, hi) & t.mask;
-    for (;;) {
-        const uint32_t tg = t.tag[slot];
-        if (tg == kTagEmpty) return kEmpty;
-        if (tg == ready && key_eq(&t.keys[2 * slot], lo, hi)) return slot;
-        slot = (slot + 1) & t.mask;
     }
 }
 

@@ -73,6 +73,8 @@ extern "C" int rf_graph_set_part(rf_graph* gr, const rf_graph_part* p) {
     // (a graph never recomputed only wrote its inputs: its next step is full)
     if (gr->initialized && gr->marked)
         return fail(RF_EPRECONDITION, "set_part: input slots set since the last recompute");
+    // the change feed reads the lists of single-graph plain steps (rf_graph_feed_open)
+    if (gr->feed) return fail(RF_EPRECONDITION, "set_part: the graph has a change feed open");
     graph_part_release(gr);
     auto* P = new GraphPart();
     gr->part = P;

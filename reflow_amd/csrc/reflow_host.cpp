@@ -740,6 +740,67 @@ uint64_t Eval::Recompute(bool full) {
     return n;
 }
 
+// ---- change feed ---------------------------------------------------------------
+void Eval::FeedOpen(const std::vector<uint64_t>* mask_words) {
+    if (mask_words && mask_words->size() < ((size_t)n_slots_ + 63) / 64)
+        throw Error(RF_EINVAL, "FeedOpen: the mask has fewer words than ceil(slots / 64)");
+    Check(rf_graph_feed_open(g_, mask_words ? mask_words->data() : nullptr));
+}
+
+void Eval::FeedClose() { Check(rf_graph_feed_close(g_)); }
+
+rf_graph_feed_stats Eval::FeedStats() const {
+    rf_graph_feed_stats st{};
+    Check(rf_graph_feed_stats_get(g_, &st));
+    return st;
+}
+
+std::vector<Eval::Changed> Eval::FeedPoll(uint64_t cap, bool force_scan, uint64_t* found) {
+    cap = std::min<uint64_t>(cap, FeedStats().tracked_slots);
+    std::vector<uint32_t> slots(std::max<uint64_t>(cap, 1));
+    std::vector<uint8_t> dig(32 * std::max<uint64_t>(cap, 1));
+    uint64_t n = 0, w = 0;
+    Check(rf_graph_feed_poll(g_, force_scan ? RF_FEED_FORCE_SCAN : 0u, cap, slots.data(), dig.data(), &n, &w));
+    std::vector<Changed> out(w);
+    for (uint64_t i = 0; i < w; ++i) {
+        out[i].slot = slots[i];
+        memcpy(out[i].digest.b.data(), &dig[32 * i], 32);
+    }
+    if (found) *found = n;
+    return out;
+}
+
+std::vector<Eval::Looked> Eval::FeedLookup(Liveset* live, Assoc& a, AssocKind kind, uint64_t cap, uint64_t* found) {
+    cap = std::max<uint64_t>(std::min<uint64_t>(cap, FeedStats().tracked_slots), 1);
+    rf_ctx* ctx = e_.ctx();
+    // one device block: slots, keys, values, status, {found, written}
+    const uint64_t o_keys = (4 * cap + 31) / 32 * 32, o_vals = o_keys + 32 * cap, o_st = o_vals + 32 * cap,
+                   o_n2 = (o_st + cap + 15) / 16 * 16, bytes = o_n2 + 16;
+    void* d = nullptr;
+    Check(rf_malloc(ctx, bytes, &d));
+    struct Free {
+        rf_ctx* c;
+        void* p;
+        ~Free() { rf_free(c, p); }
+    } guard{ctx, d};
+    uint8_t* b = static_cast<uint8_t*>(d);
+    Check(rf_graph_feed_lookup_device(g_, live ? live->b_ : nullptr, a.a_, (int)kind, 0u, cap, b, b + o_keys, b + o_st,
+                                      b + o_vals, b + o_n2, nullptr));
+    std::vector<uint8_t> h(bytes);
+    Check(rf_memcpy_d2h(ctx, h.data(), d, bytes));  // (on the context's stream: after the lookup)
+    uint64_t n2[2];
+    memcpy(n2, &h[o_n2], 16);
+    std::vector<Looked> out(n2[1]);
+    for (uint64_t i = 0; i < n2[1]; ++i) {
+        memcpy(&out[i].slot, &h[4 * i], 4);
+        memcpy(out[i].key.b.data(), &h[o_keys + 32 * i], 32);
+        memcpy(out[i].value.b.data(), &h[o_vals + 32 * i], 32);
+        out[i].status = h[o_st + i];
+    }
+    if (found) *found = n2[0];
+    return out;
+}
+
 void Eval::fetch() const {
     if (cache_ok_) return;
     std::vector<uint32_t> idx(n_slots_);
