@@ -612,6 +612,120 @@ int rf_graph_piece_slots(const rf_graph_piece *p, const uint32_t **global_of_loc
 int rf_flow_dirty(rf_ctx *ctx, uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps,
                   const uint8_t *is_extern, int no_cache_extern, uint8_t *dirty);
 
+/* ---- Evaluation plan: Eval.todo + Eval.lookup, top-down (eval.go:902-955,
+ * 1163-1269) ----
+ * Which nodes have to run, and which are cached: from the roots, a cacheable
+ * node that is not dirty is looked up; a hit ends the walk there, a miss makes
+ * the node TODO and its Deps are visited.  The reference runs one goroutine
+ * per node and one Assoc.Get per key (the batching its comments ask for,
+ * eval.go:403-405, 1190-1201); here the whole walk runs on the device as a
+ * frontier traversal whose cut-off per node is the fused liveset probe +
+ * assoc Get of rf_graph_feed_lookup_device.  An rf_eval_plan owns one Flow
+ * graph's structure on the device: opened once, run many times.
+ * A reached node i is looked up iff it is CACHEABLE (eval.go:908-913), not
+ * INVALID, has at least one key (eval.go:1183-1188) and, under
+ * no_cache_extern, is neither dirty (rf_flow_dirty's closure, eval.go:910)
+ * nor an EXTERN nor a listed root (eval.go:1173).  It is a HIT iff one of its
+ * keys, not ruled out by the liveset, has a nonzero value in the assoc under
+ * `kind`; otherwise it is TODO and every dep not reached yet is reached.  A
+ * node flagged DONE that is reached is DONE and is not expanded.  A node's
+ * state depends on the node alone and the reached set is a closure, so every
+ * result is independent of visit order and identical from run to run.
+ * Out of scope: bottom-up mode (eval.go:940-941: its lookups wait for values
+ * only the host has), dep.Err short-circuiting (eval.go:924-929), MapFlow,
+ * Parent and continuations (Deps only, as Eval.todo), partitioned graphs.
+ * Device footprint of a plan (rf_eval_plan_stats' device_bytes): per node
+ * 8 B dep pointer + 8 B key pointer + 4 B queue entry + 4 B hit-row index +
+ * 4 B of flag / state / which / found bytes + bitmaps; 4 B per dep; 4 B per
+ * key slot; 32 B per node that has keys (the hits' values, copied out of the
+ * assoc at lookup time so a later growth or compaction cannot stale them);
+ * plus, for the host-form calls, 32 B per key row and the list staging. */
+typedef struct rf_eval_plan rf_eval_plan;
+/* node flags */
+#define RF_PLAN_F_CACHEABLE 1u /* OpIntern, OpExec or OpExtern */
+#define RF_PLAN_F_EXTERN 2u    /* OpExtern */
+#define RF_PLAN_F_INVALID 4u   /* Eval.Invalidate said so (eval.go:890-899, 1173) */
+#define RF_PLAN_F_DONE 8u      /* already FlowDone: left alone, a satisfied dep */
+/* node states */
+#define RF_PLAN_UNSEEN 0 /* never reached: beneath hits or done nodes, or unreachable */
+#define RF_PLAN_TODO 1
+#define RF_PLAN_READY 2  /* TODO and every dep DONE or HIT (vacuous with no deps): what
+                            todo turns into FlowNeedTransfer / FlowReady (eval.go:930-953) */
+#define RF_PLAN_HIT 3
+#define RF_PLAN_DONE 4   /* flagged done and reached */
+#define RF_PLAN_MAX_KEYS 8
+typedef struct {
+    uint64_t n_nodes;
+    uint32_t depth;       /* nodes on the longest path: the bound on rounds */
+    uint32_t rounds;      /* round launches of the last run / reject */
+    uint32_t round_batch; /* rounds enqueued between two host reads */
+    uint32_t round_lanes; /* lanes of one round launch (a fixed grid that strides) */
+    uint32_t list_tile;   /* nodes per tile of the list's mark / scan / scatter */
+    uint32_t reserved;
+    uint64_t counts[5];   /* nodes per state after the last run / reject */
+    uint64_t looked_up;   /* nodes looked up by the last run / reject */
+    uint64_t keys_probed; /* their keys that went to the assoc */
+    uint64_t keys_filtered; /* their keys the liveset ruled out */
+    uint64_t device_bytes;
+} rf_eval_plan_stats;
+/* Node i's Deps are deps[dep_ptr[i] .. dep_ptr[i+1]) (rf_flow_dirty's CSR; a
+ * dep may be listed twice); flags: one RF_PLAN_F_* byte per node; node i's
+ * CacheKeys (flow.go:796-802, most concrete first) are key rows
+ * [key_ptr[i], key_ptr[i+1]): at most RF_PLAN_MAX_KEYS, zero keys = the lookup
+ * fails; key_slots (may be NULL): per key row, the slot of an rf_graph's slot
+ * table that holds it.  RF_EINVAL for pointers that are not monotone, deps
+ * out of range, a cycle, too many keys.  n < 2^32. */
+int rf_eval_plan_open(rf_ctx *ctx, uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, const uint8_t *flags,
+                      const uint64_t *key_ptr, const uint32_t *key_slots, rf_eval_plan **out);
+/* The structural checks of rf_eval_plan_open and *depth (may be NULL; nodes on
+ * the longest path) on the host alone: no context, no device. */
+int rf_eval_plan_check(uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, uint32_t *depth);
+void rf_eval_plan_close(rf_eval_plan *p);
+/* Replace the flag bytes of the listed nodes (after a node ran: DONE; after an
+ * invalidation).  Results of the last run stay as they are. */
+int rf_eval_plan_set_flags(rf_eval_plan *p, const uint32_t *nodes, const uint8_t *flags, uint64_t n);
+/* Run from `roots` (host array; duplicates are harmless).  Keys: with g, row r
+ * is slot key_slots[r] of g's slot table (needs key_slots at open, and g
+ * recomputed with no input change pending: RF_EPRECONDITION otherwise); else
+ * d_keys32, device rows in key_ptr order.  live may be NULL; a key it does not
+ * contain is not looked up and counts as NotExist, as
+ * rf_graph_feed_lookup_device.  Every object of one context (RF_EINVAL).  The
+ * call holds the context's lock, so no Put swaps the table under it, and
+ * returns when the plan is complete. */
+int rf_eval_plan_run(rf_eval_plan *p, const uint32_t *roots, uint64_t n_roots, int no_cache_extern, rf_graph *g,
+                     const void *d_keys32, rf_bloom *live, rf_assoc *a, int kind, void *stream);
+int rf_eval_plan_run_host(rf_eval_plan *p, const uint32_t *roots, uint64_t n_roots, int no_cache_extern,
+                          const uint8_t *keys32, rf_bloom *live, rf_assoc *a, int kind);
+/* The caller's post-checks failed for these hits (no fsid that unmarshals,
+ * missing files, RecomputeEmpty: eval.go:1210-1246): they become TODO, their
+ * deps join the frontier and the traversal goes on to its fixed point, with
+ * the no_cache_extern of the last run; the other states are kept.  Every
+ * listed node must be a HIT: RF_EINVAL otherwise, the plan untouched.  With
+ * an unchanged assoc and liveset the result equals a fresh run with
+ * RF_PLAN_F_INVALID on those nodes. */
+int rf_eval_plan_reject(rf_eval_plan *p, const uint32_t *nodes, uint64_t n, rf_graph *g, const void *d_keys32,
+                        rf_bloom *live, rf_assoc *a, int kind, void *stream);
+int rf_eval_plan_reject_host(rf_eval_plan *p, const uint32_t *nodes, uint64_t n, const uint8_t *keys32,
+                             rf_bloom *live, rf_assoc *a, int kind);
+/* Results of the last run / reject.  state: one RF_PLAN_* byte per node. */
+int rf_eval_plan_states(rf_eval_plan *p, uint8_t *state);
+int rf_eval_plan_states_device(rf_eval_plan *p, const void **d_state);
+/* The nodes in `state`, strictly ascending (a tile mark / scan / scatter over
+ * the state array, never arrival order).  For RF_PLAN_HIT each listed node
+ * also gets which (index of its first key with a value), vals32 (that value)
+ * and key_found (bit j: key j has a value -- every key of a looked-up node is
+ * probed, so read repair can be precise); any of the three may be NULL.
+ * *found = the nodes in the state; if *found > cap: RF_EINVAL, *found still
+ * set, and nothing at or beyond cap is written (cap 0 counts; the outputs
+ * may then be NULL).  The device form writes ranks below cap and *d_found
+ * (u64) on `stream`; the caller compares. */
+int rf_eval_plan_list(rf_eval_plan *p, int state, uint64_t cap, uint32_t *nodes, uint8_t *which, uint8_t *vals32,
+                      uint8_t *key_found, uint64_t *found);
+int rf_eval_plan_list_device(rf_eval_plan *p, int state, uint64_t cap, void *d_nodes, void *d_which,
+                             void *d_vals32, void *d_key_found, void *d_found /* u64 */, void *stream);
+/* size = sizeof(rf_eval_plan_stats) of the caller's header. */
+int rf_eval_plan_stats_get(rf_eval_plan *p, rf_eval_plan_stats *out, uint64_t size);
+
 /* ---- K4: bloomlive / assoc probe (bloom.go:182-190, bloomlive.go:30-36) --
  * Filters cache-key lookups before Assoc.Get (eval.go:1202-1220) and serves
  * Liveset.Contains for Repository.Collect (repository/file/repository.go:304-327). */

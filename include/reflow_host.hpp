@@ -460,6 +460,9 @@ class Eval {
     Digest FlowDigest(const Flow* f) const;
     std::optional<Digest> PhysicalDigest(const Flow* f) const;
     std::vector<Digest> CacheKeys(const Flow* f) const;
+    // The slots of the graph's table that hold CacheKeys(f), in the same order
+    // (an EvalPlan's key_slots).
+    std::vector<uint32_t> CacheKeySlots(const Flow* f) const;
     // Change one File ID wherever Fileset values reference it (needs file_slots).
     void SetFileID(const Digest& old_id, const Digest& new_id);
     uint64_t Recompute(bool full = false);
@@ -493,6 +496,7 @@ class Eval {
 
    private:
     friend Flow* Canonicalize(Engine&, FlowArena&, Flow*, Config, const std::string&, std::unique_ptr<Eval>*);
+    friend class EvalPlan;  // (Run / Reject with keys from the graph)
     using Holes = std::vector<std::pair<uint32_t, uint32_t>>;  // (byte pos, slot)
     // File IDs referenced from a job's material (file slots): (its hole's
     // index in the job, the ID) -- slots are given after the parallel phase
@@ -566,7 +570,8 @@ class Liveset {
                                                       const std::vector<int64_t>& sizes);
 
    private:
-    friend class Eval;  // (FeedLookup)
+    friend class Eval;      // (FeedLookup)
+    friend class EvalPlan;  // (Run / Reject)
     explicit Liveset(rf_bloom* b) : b_(b) {}
     rf_bloom* b_ = nullptr;
 };
@@ -618,10 +623,58 @@ class Assoc {
     std::pair<uint64_t, uint64_t> Stats();  // (occupied, capacity)
 
    private:
-    friend class Eval;  // (FeedLookup)
+    friend class Eval;      // (FeedLookup)
+    friend class EvalPlan;  // (Run / Reject)
     Assoc() = default;
     rf_assoc* a_ = nullptr;
 };
 void Delete(Assoc& a, AssocKind kind, const Digest& k);  // assoc.go:40-43
+
+// Eval.todo + Eval.lookup in top-down mode for a whole Flow graph, on the
+// device (rf_eval_plan_*; eval.go:902-955, 1163-1269): which nodes have to
+// run and which are cached.  Nodes are numbered by the caller: node i's Deps
+// are deps[dep_ptr[i] .. dep_ptr[i+1]), its RF_PLAN_F_* flags flags[i], its
+// cache keys (CacheKeys order) key rows [key_ptr[i], key_ptr[i+1]).  Opened
+// once, run once per scheduling round.
+class EvalPlan {
+   public:
+    // key_slots (optional): per key row its slot in an Eval's graph
+    // (Eval::CacheKeySlots), for the Run / Reject forms that take the Eval.
+    EvalPlan(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+             const std::vector<uint8_t>& flags, const std::vector<uint64_t>& key_ptr,
+             const std::vector<uint32_t>* key_slots = nullptr);
+    ~EvalPlan();
+    EvalPlan(const EvalPlan&) = delete;
+    EvalPlan& operator=(const EvalPlan&) = delete;
+    // The structural checks alone, on the host: the depth bound (nodes on the
+    // longest path); throws Error(RF_EINVAL) for a cycle or a malformed CSR.
+    static uint32_t Check(const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps);
+    void SetFlags(const std::vector<uint32_t>& nodes, const std::vector<uint8_t>& flags);
+    // keys: one row per key_ptr row; live may be null.
+    void Run(const std::vector<uint32_t>& roots, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+             AssocKind kind, bool no_cache_extern = false);
+    // keys from ev's graph (recomputed, nothing pending) through key_slots
+    void Run(const std::vector<uint32_t>& roots, Eval& ev, Liveset* live, Assoc& a, AssocKind kind,
+             bool no_cache_extern = false);
+    // These hits failed the caller's checks (eval.go:1210-1246): they become
+    // TODO and the traversal goes on beneath them.
+    void Reject(const std::vector<uint32_t>& nodes, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+                AssocKind kind);
+    void Reject(const std::vector<uint32_t>& nodes, Eval& ev, Liveset* live, Assoc& a, AssocKind kind);
+    std::vector<uint8_t> States();            // one RF_PLAN_* per node
+    std::vector<uint32_t> List(int state);    // ascending node ids
+    struct Hit {
+        uint32_t node;
+        int which;          // index of its first key with a value
+        Digest value;       // that value (the Fileset id)
+        uint8_t key_found;  // bit j: key j has a value
+    };
+    std::vector<Hit> Hits();  // ascending node ids
+    rf_eval_plan_stats Stats();
+
+   private:
+    rf_eval_plan* p_ = nullptr;
+    uint64_t n_keys_ = 0;
+};
 
 }  // namespace reflow

@@ -28,6 +28,10 @@ RF_PREFIX_RACE, RF_PREFIX_WAIT, RF_PREFIX_MISS = 0, 1, 2
 RF_FEED_FORCE_SCAN = 1
 RF_FEED_NONE, RF_FEED_LISTED, RF_FEED_SCAN = 0, 1, 2
 FEED_TILE_SLOTS = 8192
+# evaluation plan (rf_eval_plan_*): node flags, node states, keys per node
+RF_PLAN_F_CACHEABLE, RF_PLAN_F_EXTERN, RF_PLAN_F_INVALID, RF_PLAN_F_DONE = 1, 2, 4, 8
+RF_PLAN_UNSEEN, RF_PLAN_TODO, RF_PLAN_READY, RF_PLAN_HIT, RF_PLAN_DONE = range(5)
+RF_PLAN_MAX_KEYS = 8
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -64,6 +68,10 @@ EXPORTS = [
     "rf_graph_piece_free", "rf_graph_piece_desc", "rf_graph_piece_part", "rf_graph_piece_slots",
     "rf_graph_feed_open", "rf_graph_feed_close", "rf_graph_feed_poll", "rf_graph_feed_poll_device",
     "rf_graph_feed_lookup_device", "rf_graph_feed_stats_get",
+    "rf_eval_plan_open", "rf_eval_plan_check", "rf_eval_plan_close", "rf_eval_plan_set_flags",
+    "rf_eval_plan_run", "rf_eval_plan_run_host", "rf_eval_plan_reject", "rf_eval_plan_reject_host",
+    "rf_eval_plan_states", "rf_eval_plan_states_device", "rf_eval_plan_list", "rf_eval_plan_list_device",
+    "rf_eval_plan_stats_get",
 ]
 
 
@@ -259,6 +267,16 @@ class GraphFeedStats(ctypes.Structure):
                 ("device_bytes", ctypes.c_uint64)]
 
 
+class EvalPlanStats(ctypes.Structure):
+    """rf_eval_plan_stats: counts[state] and the lookup figures are those of the last run / reject."""
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("depth", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
+                ("round_batch", ctypes.c_uint32), ("round_lanes", ctypes.c_uint32),
+                ("list_tile", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("counts", ctypes.c_uint64 * 5), ("looked_up", ctypes.c_uint64),
+                ("keys_probed", ctypes.c_uint64), ("keys_filtered", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -405,6 +423,17 @@ def lib():
             "rf_graph_feed_poll_device": ([vp, u32, u64, vp, vp, vp, vp], i32),
             "rf_graph_feed_lookup_device": ([vp, vp, vp, i32, u32, u64, vp, vp, vp, vp, vp, vp], i32),
             "rf_graph_feed_stats_get": ([vp, vp], i32),
+            "rf_eval_plan_open": ([vp, u64, vp, vp, vp, vp, vp, vp], i32),
+            "rf_eval_plan_check": ([u64, vp, vp, vp], i32), "rf_eval_plan_close": ([vp], None),
+            "rf_eval_plan_set_flags": ([vp, vp, vp, u64], i32),
+            "rf_eval_plan_run": ([vp, vp, u64, i32, vp, vp, vp, vp, i32, vp], i32),
+            "rf_eval_plan_run_host": ([vp, vp, u64, i32, vp, vp, vp, i32], i32),
+            "rf_eval_plan_reject": ([vp, vp, u64, vp, vp, vp, vp, i32, vp], i32),
+            "rf_eval_plan_reject_host": ([vp, vp, u64, vp, vp, vp, i32], i32),
+            "rf_eval_plan_states": ([vp, vp], i32), "rf_eval_plan_states_device": ([vp, vp], i32),
+            "rf_eval_plan_list": ([vp, i32, u64, vp, vp, vp, vp, vp], i32),
+            "rf_eval_plan_list_device": ([vp, i32, u64, vp, vp, vp, vp, vp, vp], i32),
+            "rf_eval_plan_stats_get": ([vp, vp, u64], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -1290,6 +1319,141 @@ class Assoc:
     def close(self):
         if self._h:
             lib().rf_assoc_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def eval_plan_check(dep_ptr, deps) -> int:
+    """rf_eval_plan_check (host only): the depth bound (nodes on the longest
+    path) of a node graph in CSR form; RfError RF_EINVAL for pointers that are
+    not monotone, a dep out of range or a cycle."""
+    dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+    de = np.ascontiguousarray(deps, dtype=np.uint32)
+    depth = ctypes.c_uint32()
+    _check(lib().rf_eval_plan_check(max(len(dp) - 1, 0), _ptr(dp) if len(dp) else None,
+                                    _ptr(de) if len(de) else None, ctypes.byref(depth)))
+    return depth.value
+
+
+class EvalPlan:
+    """rf_eval_plan: Eval.todo + Eval.lookup in top-down mode for a whole Flow
+    graph, on the device.  dep_ptr / deps: the nodes' Deps in CSR form; flags:
+    one RF_PLAN_F_* byte per node; key_ptr: node i's cache keys are key rows
+    [key_ptr[i], key_ptr[i+1]); key_slots: per key row, a slot of a Graph's
+    slot table (for run(graph=...))."""
+
+    def __init__(self, ctx: Context, dep_ptr, deps, flags, key_ptr, key_slots=None):
+        self.ctx = ctx
+        dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+        de = np.ascontiguousarray(deps, dtype=np.uint32)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        kp = np.ascontiguousarray(key_ptr, dtype=np.uint64)
+        ks = None if key_slots is None else np.ascontiguousarray(key_slots, dtype=np.uint32)
+        self.n = len(fl)
+        self.n_keys = int(kp[-1]) if len(kp) else 0
+        self._h = ctypes.c_void_p()
+        _check(lib().rf_eval_plan_open(ctx.handle, self.n, _ptr(dp) if self.n else None,
+                                       _ptr(de) if len(de) else None, _ptr(fl) if self.n else None,
+                                       _ptr(kp) if self.n else None,
+                                       None if ks is None else (_ptr(ks) if len(ks) else _ptr(np.zeros(1, np.uint32))),
+                                       ctypes.byref(self._h)))
+
+    def set_flags(self, nodes, flags):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert len(nd) == len(fl)
+        _check(lib().rf_eval_plan_set_flags(self._h, _ptr(nd) if len(nd) else None, _ptr(fl) if len(fl) else None,
+                                            len(nd)))
+
+    @staticmethod
+    def _h_of(o):
+        return None if o is None else o._h
+
+    def run(self, roots, assoc, kind, keys=None, graph=None, d_keys=None, live=None, no_cache_extern=False,
+            stream=None):
+        """One plan from `roots`.  Keys: keys (host rows in key_ptr order:
+        rf_eval_plan_run_host), or d_keys (device rows) / graph (its slot table
+        through key_slots): rf_eval_plan_run on `stream`."""
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        rp = _ptr(r) if len(r) else None
+        if graph is None and d_keys is None:
+            k = np.ascontiguousarray(keys if keys is not None else np.zeros(0, np.uint8), dtype=np.uint8).reshape(-1)
+            assert len(k) == 32 * self.n_keys
+            _check(lib().rf_eval_plan_run_host(self._h, rp, len(r), int(bool(no_cache_extern)),
+                                               _ptr(k) if len(k) else None, self._h_of(live), assoc._h, kind))
+        else:
+            _check(lib().rf_eval_plan_run(self._h, rp, len(r), int(bool(no_cache_extern)), self._h_of(graph),
+                                          d_keys, self._h_of(live), assoc._h, kind, stream))
+
+    def reject(self, nodes, assoc, kind, keys=None, graph=None, d_keys=None, live=None, stream=None):
+        """rf_eval_plan_reject(_host): these hits failed the caller's checks."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        np_ = _ptr(nd) if len(nd) else None
+        if graph is None and d_keys is None:
+            k = np.ascontiguousarray(keys if keys is not None else np.zeros(0, np.uint8), dtype=np.uint8).reshape(-1)
+            assert len(k) == 32 * self.n_keys
+            _check(lib().rf_eval_plan_reject_host(self._h, np_, len(nd), _ptr(k) if len(k) else None,
+                                                  self._h_of(live), assoc._h, kind))
+        else:
+            _check(lib().rf_eval_plan_reject(self._h, np_, len(nd), self._h_of(graph), d_keys, self._h_of(live),
+                                             assoc._h, kind, stream))
+
+    def states(self) -> np.ndarray:
+        out = np.zeros(max(self.n, 1), dtype=np.uint8)
+        _check(lib().rf_eval_plan_states(self._h, _ptr(out)))
+        return out[:self.n]
+
+    def states_device(self) -> int:
+        p = ctypes.c_void_p()
+        _check(lib().rf_eval_plan_states_device(self._h, ctypes.byref(p)))
+        return p.value
+
+    def count(self, state) -> int:
+        n = ctypes.c_uint64()
+        rc = lib().rf_eval_plan_list(self._h, state, 0, None, None, None, None, ctypes.byref(n))
+        if rc != RF_OK and not (rc == RF_EINVAL and n.value):
+            _check(rc)
+        return n.value
+
+    def list(self, state, cap=None, poison=None):
+        """rf_eval_plan_list: (nodes uint32 [found], which uint8, vals [found, 32],
+        key_found uint8), ascending by node; the last three only carry data for
+        RF_PLAN_HIT.  cap: the buffers' rows (default: the count); poison: the
+        byte the buffers are filled with first.  RfError(RF_EINVAL) with
+        .needed = found and .buffers = the four arrays when short."""
+        cap = self.count(state) if cap is None else int(cap)
+        fill = 0 if poison is None else poison
+        nodes = np.full(max(cap, 1), fill * 0x01010101, dtype=np.uint32)
+        which = np.full(max(cap, 1), fill, dtype=np.uint8)
+        vals = np.full((max(cap, 1), 32), fill, dtype=np.uint8)
+        kf = np.full(max(cap, 1), fill, dtype=np.uint8)
+        n = ctypes.c_uint64()
+        rc = lib().rf_eval_plan_list(self._h, state, cap, _ptr(nodes), _ptr(which), _ptr(vals), _ptr(kf),
+                                     ctypes.byref(n))
+        if rc != RF_OK:
+            err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+            err.needed = n.value
+            err.buffers = (nodes, which, vals, kf)
+            raise err
+        return nodes[:n.value], which[:n.value], vals[:n.value], kf[:n.value]
+
+    def list_device(self, state, cap, d_nodes, d_which, d_vals, d_key_found, d_found, stream=None):
+        _check(lib().rf_eval_plan_list_device(self._h, state, cap, d_nodes, d_which, d_vals, d_key_found, d_found,
+                                              stream))
+
+    def stats(self) -> EvalPlanStats:
+        s = EvalPlanStats()
+        _check(lib().rf_eval_plan_stats_get(self._h, ctypes.byref(s), ctypes.sizeof(s)))
+        return s
+
+    def close(self):
+        if self._h:
+            lib().rf_eval_plan_close(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

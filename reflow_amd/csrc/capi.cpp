@@ -40,6 +40,7 @@
 #include "graph_internal.h"
 #include "host_par.h"
 #include "host_sha.h"
+#include "plan_internal.h"
 #include "reflow_hip.h"
 #include "walk.h"
 #include "wire.h"
@@ -3182,6 +3183,12 @@ extern "C" int rf_assoc_stats(rf_assoc* a, uint64_t* occupied, uint64_t* capacit
     if (capacity) *capacity = a->cap;
     return RF_OK;
 }
+
+// ---- the evaluation plan's view of the liveset and the assoc (plan_internal.h) --
+rf_ctx* rf::bloom_ctx(rf_bloom* b) { return b->ctx; }
+const BloomDev& rf::bloom_dev(rf_bloom* b) { return b->b; }
+rf_ctx* rf::assoc_ctx(rf_assoc* a) { return a->ctx; }
+AssocView rf::assoc_view(rf_assoc* a) { return a->view(); }
 
 // ---- scan, compaction, save / restore ---------------------------------------
 // The scan's two steps on stream s (ctx->mu held, so the table stays put

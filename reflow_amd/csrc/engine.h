@@ -370,4 +370,69 @@ hipError_t launch_feed_compact(const GraphDev& g, const FeedDev& f, uint64_t cap
 hipError_t launch_feed_lookup(const BloomDev* live, const AssocView& t, uint32_t kind, const uint8_t* keys,
                               const uint64_t* n2, uint64_t max_n, uint8_t* status, uint8_t* vals, hipStream_t s);
 
+// ---- K7: top-down evaluation plan (k7_plan.hip, eval_plan.cpp) -----------------
+// Node flags (RF_PLAN_F_*) and states (RF_PLAN_*) as include/reflow_hip.h.
+constexpr uint32_t kPlanBlock = 256;
+constexpr uint32_t kPlanMaxGrid = 1024;   // the round kernel's fixed grid: at most this many workgroups
+constexpr uint32_t kPlanListTile = 1024;  // nodes per list tile: 256 lanes of four state bytes
+constexpr uint32_t kPlanMaxKeys = 8;
+// control words (u32) of a plan, device memory
+enum : uint32_t {
+    kPlanLo = 0,      // the next round's frontier is queue[lo, hi)
+    kPlanHi,
+    kPlanTail,        // queue entries appended so far
+    kPlanArrived,     // workgroups of the running round that are through (zero between launches)
+    kPlanHits,        // hit rows handed out
+    kPlanLooked,      // nodes looked up
+    kPlanProbed,      // keys that went to the assoc
+    kPlanFiltered,    // keys the liveset ruled out
+    kPlanBad,         // reject: a listed node that is not a hit
+    kPlanCounts = 16,  // [5] nodes per state
+    kPlanWords = 32,
+};
+struct PlanDev {
+    uint32_t n = 0;
+    const uint64_t* dep_ptr = nullptr;  // [n+1]
+    const uint32_t* deps = nullptr;
+    const uint8_t* flags = nullptr;     // [n]
+    const uint64_t* key_ptr = nullptr;  // [n+1]
+    const uint32_t* key_slots = nullptr;  // [K] or null
+    uint32_t* claim = nullptr;   // [ceil(n/32)] bit i: node i was reached
+    uint32_t* rootbit = nullptr; // [ceil(n/32)] bit i: node i is a listed root
+    uint8_t* state = nullptr;    // [n rounded up to whole list tiles]
+    uint8_t* which = nullptr;    // [n] a hit's first key with a value
+    uint8_t* found = nullptr;    // [n] a looked-up node's found mask
+    uint32_t* hitrow = nullptr;  // [n] a hit's row in rows
+    uint4* rows = nullptr;       // [2 * row_cap] the hits' values, in arrival order
+    uint32_t row_cap = 0;        // nodes with at least one key: no run has more hits
+    uint32_t* queue = nullptr;   // [n] every reached node once, in arrival order
+    uint32_t* ctl = nullptr;     // [kPlanWords]
+};
+// what a run reads its keys, liveset and assoc from
+struct PlanLook {
+    const uint8_t* keys = nullptr;     // rows in key_ptr order, or (with slots) the graph's slot table
+    bool by_slot = false;
+    const uint32_t* dirty = nullptr;   // bit i: Eval.dirty(node i); null without NoCacheExtern
+    int no_cache_extern = 0;
+    const uint64_t* words = nullptr;   // the liveset's words (null: no liveset), its device length,
+    const uint64_t* len_dev = nullptr; // m, floor((2^64-1)/m) and k, as k6_feed_lookup takes them
+    uint64_t m = 1, mu = 0;
+    uint32_t k = 0;
+    AssocView t{};
+    uint32_t kind = 0;
+};
+uint32_t plan_grid(uint32_t n);
+hipError_t launch_plan_set_flags(uint8_t* flags, const uint32_t* nodes, const uint8_t* vals, uint32_t n,
+                                 hipStream_t s);
+hipError_t launch_plan_seed(const PlanDev& p, const uint32_t* roots, uint32_t n_roots, hipStream_t s);
+hipError_t launch_plan_rounds(const PlanDev& p, const PlanLook& l, uint32_t rounds, hipStream_t s);
+// reject: bad word = a listed node that is no hit; then the listed nodes become TODO and their deps are queued
+hipError_t launch_plan_reject_check(const PlanDev& p, const uint32_t* nodes, uint32_t n, hipStream_t s);
+hipError_t launch_plan_reject(const PlanDev& p, const uint32_t* nodes, uint32_t n, hipStream_t s);
+// after the fixed point: READY among the TODO nodes, then the per-state counts
+hipError_t launch_plan_finish(const PlanDev& p, hipStream_t s);
+// list: tile_count [ceil(n / kPlanListTile)], *d_found (u64) = nodes in `state`
+hipError_t launch_plan_list(const PlanDev& p, uint32_t state, uint64_t cap, uint32_t* tile_count, uint32_t* nodes,
+                            uint8_t* which, uint8_t* vals, uint8_t* key_found, uint64_t* d_found, hipStream_t s);
+
 }  // namespace rf

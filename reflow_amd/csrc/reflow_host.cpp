@@ -829,6 +829,15 @@ std::optional<Digest> Eval::PhysicalDigest(const Flow* f) const {
 }
 
 // CacheKeys (flow.go:796-802): most to least concrete.
+std::vector<uint32_t> Eval::CacheKeySlots(const Flow* f) const {
+    std::vector<uint32_t> slots;
+    if (const uint32_t* p = phys_slot_of(f)) slots.push_back(*p);
+    const uint32_t* l = slot_of(f);
+    if (!l) throw Error(RF_EINVAL, "CacheKeySlots: flow was not added");
+    slots.push_back(*l);
+    return slots;
+}
+
 std::vector<Digest> Eval::CacheKeys(const Flow* f) const {
     std::vector<Digest> keys;
     if (auto p = PhysicalDigest(f)) keys.push_back(*p);
@@ -1306,5 +1315,91 @@ std::pair<uint64_t, uint64_t> Assoc::Stats() {
 }
 
 void Delete(Assoc& a, AssocKind kind, const Digest& k) { a.Put(kind, Digest{}, k, Digest{}); }
+
+// ---- evaluation plan ----------------------------------------------------------
+EvalPlan::EvalPlan(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+                   const std::vector<uint8_t>& flags, const std::vector<uint64_t>& key_ptr,
+                   const std::vector<uint32_t>* key_slots) {
+    const uint64_t n = flags.size();
+    if (dep_ptr.size() != n + 1 || key_ptr.size() != n + 1) throw Error(RF_EINVAL, "EvalPlan: pointer arrays need n + 1 entries");
+    n_keys_ = key_ptr.back();
+    if (dep_ptr.back() != deps.size() || (key_slots && key_slots->size() != n_keys_))
+        throw Error(RF_EINVAL, "EvalPlan: array lengths do not match the pointers");
+    static const uint32_t none = 0;
+    reflow::Check(rf_eval_plan_open(e.ctx(), n, dep_ptr.data(), deps.data(), flags.data(), key_ptr.data(),
+                            key_slots ? (key_slots->empty() ? &none : key_slots->data()) : nullptr, &p_));
+}
+
+EvalPlan::~EvalPlan() { rf_eval_plan_close(p_); }
+
+uint32_t EvalPlan::Check(const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps) {
+    uint32_t depth = 0;
+    reflow::Check(rf_eval_plan_check(dep_ptr.empty() ? 0 : dep_ptr.size() - 1, dep_ptr.data(), deps.data(), &depth));
+    return depth;
+}
+
+void EvalPlan::SetFlags(const std::vector<uint32_t>& nodes, const std::vector<uint8_t>& flags) {
+    if (nodes.size() != flags.size()) throw Error(RF_EINVAL, "SetFlags: one flag byte per node");
+    reflow::Check(rf_eval_plan_set_flags(p_, nodes.data(), flags.data(), nodes.size()));
+}
+
+void EvalPlan::Run(const std::vector<uint32_t>& roots, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+                   AssocKind kind, bool no_cache_extern) {
+    if (keys.size() != n_keys_) throw Error(RF_EINVAL, "EvalPlan: one key per key row");
+    reflow::Check(rf_eval_plan_run_host(p_, roots.data(), roots.size(), no_cache_extern,
+                                        keys.empty() ? nullptr : keys[0].b.data(), live ? live->b_ : nullptr, a.a_, kind));
+}
+
+void EvalPlan::Run(const std::vector<uint32_t>& roots, Eval& ev, Liveset* live, Assoc& a, AssocKind kind,
+                   bool no_cache_extern) {
+    reflow::Check(rf_eval_plan_run(p_, roots.data(), roots.size(), no_cache_extern, ev.g_, nullptr,
+                                   live ? live->b_ : nullptr, a.a_, kind, nullptr));
+}
+
+void EvalPlan::Reject(const std::vector<uint32_t>& nodes, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+                      AssocKind kind) {
+    if (keys.size() != n_keys_) throw Error(RF_EINVAL, "EvalPlan: one key per key row");
+    reflow::Check(rf_eval_plan_reject_host(p_, nodes.data(), nodes.size(), keys.empty() ? nullptr : keys[0].b.data(),
+                                           live ? live->b_ : nullptr, a.a_, kind));
+}
+
+void EvalPlan::Reject(const std::vector<uint32_t>& nodes, Eval& ev, Liveset* live, Assoc& a, AssocKind kind) {
+    reflow::Check(rf_eval_plan_reject(p_, nodes.data(), nodes.size(), ev.g_, nullptr, live ? live->b_ : nullptr, a.a_,
+                                      kind, nullptr));
+}
+
+std::vector<uint8_t> EvalPlan::States() {
+    std::vector<uint8_t> st(Stats().n_nodes);
+    reflow::Check(rf_eval_plan_states(p_, st.data()));
+    return st;
+}
+
+std::vector<uint32_t> EvalPlan::List(int state) {
+    if (state < RF_PLAN_UNSEEN || state > RF_PLAN_DONE) throw Error(RF_EINVAL, "EvalPlan: unknown state");
+    std::vector<uint32_t> nodes(Stats().counts[state]);
+    uint64_t found = 0;
+    reflow::Check(rf_eval_plan_list(p_, state, nodes.size(), nodes.data(), nullptr, nullptr, nullptr, &found));
+    nodes.resize(found);
+    return nodes;
+}
+
+std::vector<EvalPlan::Hit> EvalPlan::Hits() {
+    const uint64_t cap = Stats().counts[RF_PLAN_HIT];
+    std::vector<uint32_t> nodes(cap);
+    std::vector<uint8_t> which(cap), kf(cap);
+    std::vector<Digest> vals(cap);
+    uint64_t found = 0;
+    reflow::Check(rf_eval_plan_list(p_, RF_PLAN_HIT, cap, nodes.data(), which.data(), cap ? vals[0].b.data() : nullptr,
+                                    kf.data(), &found));
+    std::vector<Hit> out(found);
+    for (uint64_t i = 0; i < found; ++i) out[i] = Hit{nodes[i], which[i], vals[i], kf[i]};
+    return out;
+}
+
+rf_eval_plan_stats EvalPlan::Stats() {
+    rf_eval_plan_stats st{};
+    reflow::Check(rf_eval_plan_stats_get(p_, &st, sizeof st));
+    return st;
+}
 
 }  // namespace reflow
