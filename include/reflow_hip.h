@@ -176,16 +176,20 @@ void rf_sha_plan_destroy(rf_sha_plan *plan);
 #define RF_SHA_NO_PREFIX 128u  /* no prefix hand-over: the split and the run as without it */
 
 /* Prefix hand-over.  A host-leg message that waits in the pool's queue has
- * its first blocks hashed by an idle duo wave meanwhile; the host thread that
- * claims it looks once whether the wave is done and, if so, resumes from the
- * wave's chaining value instead of block 0 (it never waits for the wave).
+ * its first blocks hashed by an idle duo wave meanwhile, which leaves its
+ * chaining value in host memory every few thousand blocks; the host thread
+ * that claims the message stops the wave and resumes from the latest value
+ * it finds instead of block 0 (it never waits for the wave).
  * Planned for HBM-resident plans with both legs; off with RF_SHA_NO_PREFIX,
- * or with RF_SHA_PREFIX=0 in the environment when the plan is created
- * (RF_SHA_PREFIX_ALPHA there sets the share of a message's modelled wait its
- * prefix is sized to, default 0.85). */
+ * or with RF_SHA_PREFIX=0 in the environment when the plan is created.  Read
+ * there too: RF_SHA_PREFIX_ALPHA, the share of a message's modelled wait the
+ * split is priced with (default 1.0); RF_SHA_PREFIX_CKPT, the blocks between
+ * two chaining values (a multiple of 64, default 2048); and, for tests,
+ * RF_SHA_PREFIX_PRECLAIM=1: every message counts as claimed before the
+ * launch, so each wave stops at its first value. */
 typedef struct {
     uint64_t n_prefixed;    /* host-leg messages with a prefix                 */
-    uint64_t planned_bytes; /* 64 x their prefix blocks                        */
+    uint64_t planned_bytes; /* 64 x the most blocks their waves may hash       */
     uint64_t taken, missed; /* last run: prefixes found ready / not ready      */
     uint64_t skipped_bytes; /* last run: bytes the host leg did not hash       */
 } rf_sha_prefix_stats;

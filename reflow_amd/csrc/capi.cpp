@@ -313,12 +313,14 @@ struct rf_sha_plan {
     bool ran = false;
     rf_sha_stats st{};
     // prefix hand-over (host_sched.h): pfx[i] = blocks of host task i a duo
-    // wave hashes first; hand = coherent pinned host memory, 32-byte chaining
-    // values for every host task, then their 4-byte ready flags
+    // wave hashes at most (its cap); hand = coherent pinned host memory, a
+    // PrefixRecord for every host task, then their 4-byte claimed words
     uint32_t flags = 0;
     std::vector<uint64_t> pfx;
     uint32_t n_pfx = 0;
     int pfx_mode = RF_PREFIX_RACE;
+    uint32_t pfx_ck = 1;         // 64-block chunks between two records
+    bool pfx_preclaim = false;  // RF_SHA_PREFIX_PRECLAIM: every file claimed before the launch
     DevBuf d_pfx_ids, d_pfx_blocks, d_pfx_slot;
     void* hand = nullptr;
     size_t hand_cap = 0;  // host tasks it holds
@@ -395,18 +397,30 @@ static constexpr uint64_t kLinkCalibBytes = 1ull << 30;  // a host leg this larg
 
 // Prefix hand-over (host_sched.h, DESIGN.md §5 "Prefix hand-over").
 //   kDuoBlockS        the duo chain's measured time per block (gpu_model's t_duo).
-//   kPrefixAlpha      the share of a message's modelled wait its prefix is sized
-//                     to: the wave must be done when the host claims the message,
-//                     and a host leg that runs ahead of its model claims early,
-//                     so 15 % of the wait is kept as slack.  A miss loses
-//                     nothing but the wave's work.
-//   kPrefixMinBlocks  below 4096 blocks (256 KiB, ~160 us of one host lane) a
-//                     prefix saves about what the model charges per message and
-//                     per pool wake (20 + 100 us): inside the model's own error,
-//                     so it is not worth a workgroup and a flag.
+// A prefix wave does not stop at a planned block: it leaves a chaining value
+// every kPrefixCkptBlocks blocks until the host claims the file, so the split
+// is priced with what the host is expected to find and the waves' caps are
+// sized apart from it.
+//   kPrefixAlpha      pricing: the share of a message's modelled wait the wave
+//                     is expected to have hashed when the host claims it, less
+//                     half a checkpoint interval (the latest record's mean
+//                     distance behind the wave).  1.0: on configs[1] the model
+//                     then moves 4.08 GB, under the 4.32-4.36 GB measured on
+//                     each of 20 steps (the host runs a little behind its
+//                     model, so the waves get further).  RF_SHA_PREFIX_ALPHA
+//                     sets it.
+//   kPrefixCapAlpha   caps: 1.25 x the modelled wait, cut only at the modelled
+//                     makespan -- a wave outlives a host that runs behind its
+//                     model, not the step.
+//   kPrefixCkptBlocks 2,048 blocks (32 chunks, 2.3 ms of a duo chain): the half
+//                     interval lost per file sums to ~10 MB over ~80 files,
+//                     under 0.5 % of the prefix bytes.  RF_SHA_PREFIX_CKPT sets
+//                     it (a multiple of 64).  Also the floor: a wait shorter
+//                     than one interval leaves no record to take.
 static constexpr double kDuoBlockS = 1.13e-6;
-static constexpr double kPrefixAlpha = 0.85;
-static constexpr uint64_t kPrefixMinBlocks = 4096;
+static constexpr double kPrefixAlpha = 1.0;
+static constexpr double kPrefixCapAlpha = 1.25;
+static constexpr uint64_t kPrefixCkptBlocks = 2048;
 
 // The feed rate the planner prices the host leg's HBM-resident bytes at:
 // the context's last measurement at the current width (a whole leg's bytes
@@ -439,13 +453,12 @@ extern "C" int rf_host_link(rf_ctx* ctx, double* bytes_per_s, int* measured) {
 // would not finish sooner.
 //
 // With a schedule model (hs: prefix hand-over on), host(h) is instead the
-// thread-aware replay of the pool (host_sched.h) with each message's prefix
-// taken off its bytes, and prefix_out receives the h host messages' prefixes.
+// thread-aware replay of the pool (host_sched.h) with each message's expected
+// prefix taken off its bytes (the waves' caps are sized by the caller).
 // Without one the split is exactly the per-slot model above.
 static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, std::vector<uint32_t>& order,
                        uint32_t n_cu, uint32_t flags, const HostModel& hm, uint32_t* n_host_out,
-                       uint32_t* n_solo_out, const HostSchedParams* hs = nullptr,
-                       std::vector<uint64_t>* prefix_out = nullptr) {
+                       uint32_t* n_solo_out, const HostSchedParams* hs = nullptr) {
     const uint64_t n = nb.size();
     order.resize(n);
     std::iota(order.begin(), order.end(), 0u);
@@ -519,7 +532,19 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
             best_h = a;
         }
         h = best_h;
-        if (hs && prefix_out) *prefix_out = host_schedule(slens.data(), h, *hs).prefix_blocks;
+        // A whole-file duo wave cannot be taken over part-way, and its time is
+        // known to the block, while the host leg has run up to 3 % ahead of
+        // a model calibrated by all-host runs (the split used to flip between
+        // 111 / 0 and 110 / 1 on a +-1 % calibration, a 2 % step).  With a
+        // prefix wave on it from t = 0 a big file costs the host leg only its
+        // expected suffix, so a file whose whole-file wave would end within
+        // 10 % of the leg's modelled end joins the leg while that adds at most
+        // 0.5 % to it.  gpu_t falls with h, so this ends at the first file
+        // whose wave is clear of the leg's end.
+        if (hs && h > 0) {
+            const double base = host_at(h);
+            while (h < n && gpu_t(h) > 0.9 * base && host_at(h + 1) <= 1.005 * base) ++h;
+        }
     }
     uint64_t k = 0;
     gpu_model(nbs, suf, h, n_cu, flags, &k);
@@ -543,7 +568,7 @@ static hipError_t plan_wait_side(rf_sha_plan* p) {
     return hipEventSynchronize(p->e_solo);
 }
 
-// Installs prefix[i] for host task i (all zero: none): the launch's device
+// Installs cap prefix[i] for host task i (all zero: none): the launch's device
 // arrays, and the host tasks' pointers into the hand-over memory.
 static int plan_prefixes(rf_sha_plan* p, const uint64_t* prefix) {
     const uint32_t nh = p->n_host;
@@ -553,7 +578,8 @@ static int plan_prefixes(rf_sha_plan* p, const uint64_t* prefix) {
     std::vector<uint64_t> blocks;
     for (uint32_t i = 0; i < nh; ++i) {
         p->host[i].prefix_blocks = 0;
-        p->host[i].mid = p->host[i].ready = nullptr;
+        p->host[i].rec = nullptr;
+        p->host[i].claimed = nullptr;
         if (!prefix[i]) continue;
         ids.push_back(p->host[i].id);
         blocks.push_back(prefix[i]);
@@ -567,16 +593,16 @@ static int plan_prefixes(rf_sha_plan* p, const uint64_t* prefix) {
         p->hand = nullptr;
         p->hand_cap = 0;
         const size_t want = std::max<size_t>(nh, 128);
-        HIPC(hipHostMalloc(&p->hand, 36 * want, hipHostMallocCoherent | hipHostMallocMapped));
+        HIPC(hipHostMalloc(&p->hand, (sizeof(PrefixRecord) + 4) * want, hipHostMallocCoherent | hipHostMallocMapped));
         p->hand_cap = want;
     }
-    const uint32_t* mid = static_cast<const uint32_t*>(p->hand);
-    const uint32_t* ready = mid + 8 * p->hand_cap;
+    PrefixRecord* rec = static_cast<PrefixRecord*>(p->hand);
+    uint32_t* claimed = reinterpret_cast<uint32_t*>(rec + p->hand_cap);
     for (uint32_t j = 0; j < p->n_pfx; ++j) {
         HostTask& t = p->host[slot[j]];
         t.prefix_blocks = blocks[j];
-        t.mid = mid + 8ull * slot[j];
-        t.ready = ready + slot[j];
+        t.rec = rec + slot[j];
+        t.claimed = claimed + slot[j];
     }
     hipError_t e;
     if ((e = p->d_pfx_ids.ensure(4ull * p->n_pfx)) != hipSuccess ||
@@ -630,6 +656,18 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
     const char* env_pfx = getenv("RF_SHA_PREFIX");
     const bool prefix_on = !host_resident && threads > 0 && !(env_pfx && atoi(env_pfx) == 0) &&
                            !(flags & (RF_SHA_NO_PREFIX | RF_SHA_ALL_HOST | RF_SHA_NO_HOST | RF_SHA_ONE_LANE_CHAIN));
+    // the checkpoint interval in blocks, and the PRECLAIM diagnostic (tests:
+    // every wave stops at its first record, which pins the intermediate
+    // chaining values without a race)
+    uint64_t ckpt = kPrefixCkptBlocks;
+    if (const char* v = getenv("RF_SHA_PREFIX_CKPT")) {
+        const long long b = atoll(v);
+        ARG(b >= 64 && b % 64 == 0 && b <= (1ll << 31), "RF_SHA_PREFIX_CKPT: a multiple of 64 blocks");
+        ckpt = (uint64_t)b;
+    }
+    p->pfx_ck = (uint32_t)(ckpt / 64);
+    const char* env_pre = getenv("RF_SHA_PREFIX_PRECLAIM");
+    p->pfx_preclaim = env_pre && atoi(env_pre) != 0;
     if (prefix_on) {
         hs.threads = threads;
         hs.ways = ways;
@@ -638,9 +676,20 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
         hs.t_duo = kDuoBlockS;
         hs.alpha = kPrefixAlpha;
         if (const char* a = getenv("RF_SHA_PREFIX_ALPHA")) hs.alpha = std::min(1.0, std::max(0.0, atof(a)));
-        hs.min_blocks = kPrefixMinBlocks;
+        hs.min_blocks = ckpt;
+        hs.end_frac = 1.0;
+        hs.loss_blocks = ckpt / 2;
     }
-    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo, prefix_on ? &hs : nullptr, &prefix);
+    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo, prefix_on ? &hs : nullptr);
+    if (prefix_on && n_host) {
+        // the caps: what a wave may hash if the host comes late
+        std::vector<uint64_t> slens(n_host);
+        for (uint32_t i = 0; i < n_host; ++i) slens[i] = lens[order[i]];
+        HostSchedParams hc = hs;
+        hc.alpha = hs.alpha > 0 ? kPrefixCapAlpha : 0.0;
+        hc.loss_blocks = 0;
+        prefix = host_schedule(slens.data(), n_host, hc).prefix_blocks;
+    }
     p->flags = flags;
     p->n_host = n_host;
     p->n_solo = n_solo;
@@ -744,12 +793,17 @@ static int plan_run_locked(rf_sha_plan* p, const void* d_arena, void* d_out, hip
     const uint32_t* order = p->d_order.as<uint32_t>();
     if (p->n_lanes) HIPC(hipMemsetAsync(p->d_heads.p, 0, 4 * 64, s));
     // prefix hand-overs ride in the duo launch (RF_PREFIX_MISS: left out, so
-    // every flag stays unset); the flags are reset here, on the host, once the
-    // previous run's launch can no longer set one
+    // no record appears); the records' counters and the claimed words are
+    // reset here, on the host, once the previous run's launch can no longer
+    // write one
     const bool pfx_launch = p->n_pfx && !h_arena && p->pfx_mode != RF_PREFIX_MISS;
     if (p->n_pfx) {
         HIPC(plan_wait_side(p));
-        memset(static_cast<uint32_t*>(p->hand) + 8 * p->hand_cap, 0, 4 * p->hand_cap);
+        for (const HostTask& t : p->host) {
+            if (!t.rec) continue;
+            const_cast<PrefixRecord*>(t.rec)->latest = 0;
+            *t.claimed = p->pfx_preclaim ? 1u : 0u;
+        }
     }
     p->side_ran = p->n_solo || pfx_launch;
     if (p->side_ran) {
@@ -760,8 +814,9 @@ static int plan_run_locked(rf_sha_plan* p, const void* d_arena, void* d_out, hip
         if (pfx_launch) {
             void* d_hand = nullptr;
             HIPC(hipHostGetDevicePointer(&d_hand, p->hand, 0));
+            PrefixRecord* d_rec = static_cast<PrefixRecord*>(d_hand);
             PrefixArgs pa{p->d_pfx_ids.as<uint32_t>(), p->d_pfx_blocks.as<uint64_t>(), p->d_pfx_slot.as<uint32_t>(),
-                          p->n_pfx, static_cast<uint32_t*>(d_hand), static_cast<uint32_t*>(d_hand) + 8 * p->hand_cap};
+                          p->n_pfx, p->pfx_ck, d_rec, reinterpret_cast<const uint32_t*>(d_rec + p->hand_cap)};
             HIPC(launch_sha_duo_prefix(sa, pa, p->side));
         } else {
             HIPC(launch_sha_solo(sa, p->duo, p->side));

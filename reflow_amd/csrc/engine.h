@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "diag.h"
+#include "prefix_record.h"
 
 namespace rf {
 
@@ -37,17 +38,19 @@ struct SoloArgs {
 };
 // duo: the round chain on two lanes (k1_sha256_duo); else one lane (k1_sha256_solo)
 hipError_t launch_sha_solo(const SoloArgs& a, bool duo, hipStream_t s);
-// Prefix hand-over (host_sched.h): entry j is the first blocks[j] whole blocks
-// of message ids[j]; its chaining value (eight state words, host order) goes to
-// mid[8 * slot[j] ..] and then ready[slot[j]] = 1.  mid and ready are the
-// device addresses of coherent pinned host memory the host leg polls once.
+// Prefix hand-over (host_sched.h): entry j is at most the first blocks[j]
+// whole blocks of message ids[j].  Its wave leaves the chaining value in
+// rec[slot[j]] (prefix_record.h) every ck 64-block chunks and at blocks[j],
+// and stops at the first of these after the host has set claimed[slot[j]].
+// rec and claimed are the device addresses of coherent pinned host memory.
 struct PrefixArgs {
     const uint32_t* ids;
     const uint64_t* blocks;
     const uint32_t* slot;
     uint32_t n;
-    uint32_t* mid;
-    uint32_t* ready;
+    uint32_t ck;
+    PrefixRecord* rec;
+    const uint32_t* claimed;
 };
 // One k1_sha256_duo launch: a's messages whole (digests), then pa's prefixes.
 hipError_t launch_sha_duo_prefix(const SoloArgs& a, const PrefixArgs& pa, hipStream_t s);

@@ -16,8 +16,13 @@
 
 namespace rf {
 
+// 16 MiB: the leg is bound by the D2H link, so the gap between two copies of
+// a lane is on the critical path.  Three alternating bench runs each on the
+// MI355X box: 8 MiB 55.71-56.33 GB/s, 16 MiB 57.51-57.80, 32 MiB 57.82-58.13
+// (profiles/ckpt_handover/chunk_size.txt); 32 MiB would pin twice the memory
+// (4 buffers a thread) for another 0.5 %.
 uint64_t host_chunk_bytes() {
-    static const uint64_t c = (uint64_t)std::max<long>(1, RF_DIAG_KNOB("RF_HOST_CHUNK_MB", 8)) << 20;
+    static const uint64_t c = (uint64_t)std::max<long>(1, RF_DIAG_KNOB("RF_HOST_CHUNK_MB", 16)) << 20;
     return c;
 }
 
@@ -142,6 +147,21 @@ int host_ways() {
     return w;
 }
 
+bool prefix_record_take(const PrefixRecord* rec, uint32_t st[8], uint64_t* blocks) {
+    uint32_t k = __atomic_load_n(&rec->latest, __ATOMIC_ACQUIRE);
+    for (int round = 0; k && round < 3; ++round) {
+        // the wave may be writing meanwhile: word-wise loads, checked below
+        const PrefixSlot& s = rec->slot[k & 1];
+        for (int i = 0; i < 8; ++i) st[i] = __atomic_load_n(&s.state[i], __ATOMIC_RELAXED);
+        *blocks = __atomic_load_n(&s.blocks, __ATOMIC_RELAXED);
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const uint32_t after = __atomic_load_n(&rec->latest, __ATOMIC_ACQUIRE);
+        if (prefix_copy_intact(k, after)) return true;
+        k = after;
+    }
+    return false;
+}
+
 namespace {
 // One message in flight on a host thread.  Its bytes come in chunks of C
 // (from the message start, or from the end of a prefix taken over from the
@@ -200,7 +220,18 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                 x.total = tasks[i].len;
                 host_sha_init(x.st);
                 uint64_t base = 0;
-                if (tasks[i].prefix_blocks) {  // one look at the flag, never a wait
+                if (tasks[i].rec) {  // stop the wave, take its latest record; never a wait
+                    __atomic_store_n(tasks[i].claimed, 1u, __ATOMIC_RELEASE);
+                    uint64_t blocks = 0;
+                    if (prefix_record_take(tasks[i].rec, x.st, &blocks) && blocks && blocks <= tasks[i].len / 64) {
+                        base = 64 * blocks;
+                        taken.fetch_add(1, std::memory_order_relaxed);
+                        skipped.fetch_add(base, std::memory_order_relaxed);
+                    } else {
+                        host_sha_init(x.st);
+                        missed.fetch_add(1, std::memory_order_relaxed);
+                    }
+                } else if (tasks[i].prefix_blocks) {  // one look at the flag, never a wait
                     if (__atomic_load_n(tasks[i].ready, __ATOMIC_ACQUIRE)) {
                         memcpy(x.st, tasks[i].mid, 32);
                         base = 64 * tasks[i].prefix_blocks;

@@ -15,6 +15,8 @@
 #include <thread>
 #include <vector>
 
+#include "prefix_record.h"
+
 namespace rf {
 
 // D2H chunk of one host thread (a multiple of 64: whole SHA-256 blocks);
@@ -86,7 +88,19 @@ struct HostTask {
     uint64_t prefix_blocks = 0;
     const uint32_t* mid = nullptr;
     const uint32_t* ready = nullptr;
+    // Checkpointed hand-over (prefix_record.h; both null: the protocol above).
+    // The wave keeps hashing up to prefix_blocks blocks and publishes a
+    // chaining value every few thousand of them.  The claiming thread sets
+    // *claimed, which stops the wave at its next record, and resumes from the
+    // latest record it finds (none yet: it hashes the whole message).  It
+    // still never waits.
+    const PrefixRecord* rec = nullptr;
+    uint32_t* claimed = nullptr;
 };
+
+// One look at a record: the latest intact slot into st / *blocks.  False:
+// nothing published yet (or no intact copy in three tries; st is then junk).
+bool prefix_record_take(const PrefixRecord* rec, uint32_t st[8], uint64_t* blocks);
 
 // Prefixes of one host_leg_run: found ready, found not ready, and the bytes
 // the host did not hash (64 x the taken prefixes' blocks).

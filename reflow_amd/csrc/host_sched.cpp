@@ -40,6 +40,7 @@ uint64_t replay(const uint64_t* lens, uint64_t n, const HostSchedParams& p, uint
             pb = std::min<uint64_t>((uint64_t)std::floor(p.alpha * th.t / p.t_duo), lens[i] / 64);
             longest = std::max(longest, pb);
             pb = std::min(pb, cap_blocks);
+            pb -= std::min(pb, p.loss_blocks);
             if (pb < std::max<uint64_t>(p.min_blocks, 1)) pb = 0;
         }
         out->t_start[i] = th.t;

@@ -30,6 +30,10 @@ struct HostSchedParams {
     double alpha = 0.0;        // share of a message's wait a duo wave is trusted to use
     uint64_t min_blocks = 0;   // a shorter prefix is not worth a wave: 0 blocks instead
     double end_frac = 0.9;     // longest prefix's modelled end <= end_frac x modelled makespan
+    // checkpointed hand-over: the host resumes from the wave's latest record,
+    // on average half a checkpoint interval behind the wave -- blocks taken
+    // off every prefix (0: the wave's own stopping point, as planned lengths are)
+    uint64_t loss_blocks = 0;
 };
 
 struct HostSched {

@@ -269,15 +269,39 @@ __global__ __launch_bounds__(64) void k1_sha256_solo(SoloArgs a) {
 // 64 blocks), so the chain never waits for HBM or the message schedule.
 //
 // kPrefix: the launch also carries prefix hand-overs (PrefixArgs, engine.h):
-// workgroups q >= a.n_order hash only the first pa.blocks[j] whole blocks of
-// their message -- the producer still sees the real length, so no padding
-// appears -- and leave the chaining value and a ready flag in host memory
-// for the host leg, which resumes from there (host_leg.h).
+// workgroups q >= a.n_order hash at most the first pa.blocks[j] whole blocks
+// of their message -- the producer still sees the real length, so no padding
+// appears -- and leave chaining values in host memory for the host leg, which
+// resumes from the latest one (host_leg.h).  A record is taken at the first
+// block of every pa.ck-th 64-block chunk: after that block's group 0 both
+// halves have applied the feed-forward, so Hr0..Hr3 hold the chaining value
+// of all earlier blocks in the tail's layout and the lagged chain runs on
+// undisturbed.  After publishing it the chain wave looks once at the file's
+// claimed word and leaves the answer in LDS; both waves read it behind the
+// chunk's barrier and leave the file together (no polling anywhere: a wave
+// that never sees the word set ends at pa.blocks[j], its last record).
+
+// Record k of prefix slot sl: the chaining value as it is (no byte swap) and
+// the block count into slot k & 1, then latest = k -- the host takes a slot
+// only after it has seen its number.  Lane 8 holds H0..H3, lane 0 H4..H7.
+__device__ __forceinline__ void publish_record(PrefixRecord* rec, uint32_t k, uint64_t blocks, uint32_t lane,
+                                               uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3) {
+    PrefixSlot* s = &rec->slot[k & 1];
+    if (lane == 0 || lane == 8) reinterpret_cast<uint4*>(s->state)[lane == 0 ? 1 : 0] = make_uint4(h0, h1, h2, h3);
+    if (lane == 0) s->blocks = blocks;
+    __threadfence_system();
+    if (lane == 0) __hip_atomic_store(&rec->latest, k, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <bool kPrefix>
 __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) {
     // two buffers of 64 K+W rows, then the a-lanes' k row: word 0 = 0
     // (block-start add), the rest 1 (Zt = -c)
     __shared__ __attribute__((aligned(16))) uint32_t kw[129 * kRow];
+    // the claimed word as record k found it, at stopw[k & 1]: the chain wave
+    // writes record k + 2's answer only after a barrier the producer wave
+    // reaches after it has read record k's
+    __shared__ uint32_t stopw[2];
     // wave-uniform (SGPR) so the role branches below are scalar branches and
     // each wave meets exactly one barrier per chunk
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -315,10 +339,19 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) 
         uint32_t c64 = elane ? lag::IV[2] : 0u - lag::IV[4];
         uint32_t c65 = elane ? lag::IV[1] : 0u - lag::IV[3];
         uint32_t t0, t1, t3;
+        // prefix workgroups: the chunk whose first block takes the next
+        // record, that record's number, and whether the host has the file
+        // (all three uniform over the workgroup)
+        const uint32_t sl = pfx ? pa.slot[q - a.n_order] : 0u;
+        const uint64_t span = 64ull * pa.ck;
+        uint64_t next_ck = pfx ? span : ~0ull;
+        uint32_t kk = 1;
+        bool stopped = false;
         if (wave == 1) fill_kw_rows(kw, p, len, nb, 0, lane);
         __syncthreads();
         uint32_t buf = 0;
         for (uint64_t c = 0; c < nb; c += 64, buf ^= 1) {
+            const bool ck_now = kPrefix && c == next_ck;
             if (wave == 1) {
                 if (c + 64 < nb) fill_kw_rows(&kw[(buf ^ 1) * 64 * kRow], p, len, nb, c + 64, lane);
             } else {
@@ -352,6 +385,12 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) 
                                  : RF_LAG_IN(k1, k2, v.w, vn.x), [kw0] "v"(v.x), [one] "v"(one),
                                    [zero] "v"(zero));
                 }
+                if (kPrefix && ck_now && j == 0) {
+                    // H after the c blocks before this one
+                    publish_record(pa.rec + sl, kk, c, lane, Hr0, Hr1, Hr2, Hr3);
+                    if (lane == 0)
+                        stopw[kk & 1] = __hip_atomic_load(pa.claimed + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
                 v = vn;
                 vn = vnn;
 #pragma unroll
@@ -367,8 +406,16 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) 
             }
             }
             __syncthreads();
+            if (kPrefix && ck_now) {
+                if (__builtin_amdgcn_readfirstlane(stopw[kk & 1])) {
+                    stopped = true;
+                    break;
+                }
+                next_ck += span;
+                ++kk;
+            }
         }
-        if (wave == 1) continue;
+        if (wave == 1 || (kPrefix && stopped)) continue;
         // tail: the e-lanes are done (H += X, X untouched so the a-lanes' last
         // Z reads raw e(64)); the a-lanes run rounds 62 and 63, then H += X.
         asm volatile("s_nop 1\n\t" RF_LAG_FIN("0x3", "a", "b", "c", "d")
@@ -379,13 +426,8 @@ __global__ __launch_bounds__(128) void k1_sha256_duo(SoloArgs a, PrefixArgs pa) 
                      : RF_LAG_IN(one, one, one, one));
         // lane 8 (a-lane) holds H0..H3, lane 0 (e-lane) H4..H7
         if (kPrefix && pfx) {
-            // the chaining value as it is (no byte swap), then the flag: the
-            // host takes the value only after it has seen the flag
-            const uint32_t sl = pa.slot[q - a.n_order];
-            if (lane == 0 || lane == 8)
-                reinterpret_cast<uint4*>(pa.mid + 8ull * sl)[lane == 0 ? 1 : 0] = make_uint4(Hr0, Hr1, Hr2, Hr3);
-            __threadfence_system();
-            if (lane == 0) __hip_atomic_store(pa.ready + sl, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            // the last record, at exactly the cap
+            publish_record(pa.rec + sl, kk, nb, lane, Hr0, Hr1, Hr2, Hr3);
             continue;
         }
         if (lane == 0 || lane == 8) {

@@ -53,15 +53,21 @@ def main():
         if i < args.warmup:
             continue
         rows.append((wall, s.last_ms_host, s.last_ms_solo, s.last_ms_lanes, p.taken, p.missed, p.skipped_bytes))
-        print("step %2d: wall %7.1f ms, host %7.1f, solo %7.1f, lanes %5.1f; taken %d missed %d, %.3f GB skipped"
+        # the host leg's feed: the bytes that crossed the link over its wall time
+        feed = (st.host_bytes - p.skipped_bytes) / (s.last_ms_host * 1e-3) / 1e9 if s.last_ms_host > 0 else 0.0
+        print("step %2d: wall %7.1f ms, host %7.1f, solo %7.1f, lanes %5.1f; taken %d missed %d, "
+              "%.3f of %.3f GB planned skipped; host feed %.2f GB/s"
               % (i - args.warmup, wall, s.last_ms_host, s.last_ms_solo, s.last_ms_lanes, p.taken, p.missed,
-                 p.skipped_bytes / 1e9))
+                 p.skipped_bytes / 1e9, p.planned_bytes / 1e9, feed))
     r = np.array(rows, dtype=np.float64)
     print(json.dumps({"steps": len(rows), "wall_ms_mean": round(float(r[:, 0].mean()), 2),
                       "host_ms_mean": round(float(r[:, 1].mean()), 2), "solo_ms_mean": round(float(r[:, 2].mean()), 2),
                       "solo_le_host_every_step": bool((r[:, 2] <= r[:, 1]).all()),
                       "taken": int(r[:, 4].sum()), "missed": int(r[:, 5].sum()),
                       "skipped_gb_mean": round(float(r[:, 6].mean()) / 1e9, 3),
+                      "skipped_gb_min": round(float(r[:, 6].min()) / 1e9, 3),
+                      "skipped_gb_max": round(float(r[:, 6].max()) / 1e9, 3),
+                      "planned_gb": round(ps.planned_bytes / 1e9, 3),
                       "n_prefixed": int(ps.n_prefixed), "host_bytes_gb": round(st.host_bytes / 1e9, 3)}))
     plan.close()
 
