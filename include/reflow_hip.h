@@ -730,6 +730,95 @@ int rf_eval_plan_list_device(rf_eval_plan *p, int state, uint64_t cap, void *d_n
 /* size = sizeof(rf_eval_plan_stats) of the caller's header. */
 int rf_eval_plan_stats_get(rf_eval_plan *p, rf_eval_plan_stats *out, uint64_t size);
 
+/* ---- GC liveset: Eval.collect's walk, dedup and filter build (eval.go:791-868) ----
+ * What is live, as a bloom filter, without a host walk of the graph.  An
+ * rf_liveset owns one Flow graph's edges and its nodes' current Fileset values
+ * on the device: opened once, updated as nodes finish, run once per
+ * collection.
+ * Graph: rf_eval_plan_open's CSR (an edge may be listed twice; monotone
+ * pointers, range and no cycle are checked as there; n < 2^32).  Node i's
+ * edges are its Deps; for an OpMap node the caller appends its MapFlow
+ * (eval.go:822-824).
+ * Values: a node has a value iff State == FlowDone and Value is a Fileset: its
+ * rows are the (ID, Size) of the Fileset's Map entries with List flattened
+ * recursively, exactly Fileset.N() of them (executor.go:95-102; duplicates
+ * kept, zero rows valid).  A Done node whose value is not a Fileset has no
+ * value here (the reference expands it).
+ * Walk (eval.go:809-826) from the listed roots: a reached node with a value is
+ * RF_LIVE_VALUE and is not expanded; every other reached node is
+ * RF_LIVE_WALKED and all its edges are reached; the rest stays
+ * RF_LIVE_UNSEEN.  A node's state depends on the node alone and the reached
+ * set is a closure, so every result is identical from run to run.
+ * Contributions: the RF_LIVE_VALUE nodes ascending, then each entry of
+ * `writers` in the caller's order (eval.go:827-835); a writer without a value
+ * contributes zero rows; a writer on the frontier, or listed twice,
+ * contributes twice (the reference appends a second *Fileset).
+ * nlive_est = rows over all contributions (N(), not unique); the filter is
+ * bloom.NewWithEstimates(nlive_est, 0.001) (rf_bloom_estimate, then max(1, .):
+ * bloom.go:81-83, 120-131), or bloom.New(64, 1) when nlive_est is 0
+ * (eval.go:842); its bitset length is m.  Every row's WD(ID) is added.
+ * nlive / livebytes: per contribution separately the distinct (ID, Size)
+ * pairs (Files() is a map[File]bool per value): their number and the sum of
+ * their sizes over the contributions.
+ * changed (eval.go:862): 1 on the first run, then 1 iff m, k, the length or a
+ * word differ from the previous run's filter (the object keeps it; the two
+ * alternate).  maxlivebytes: the running maximum of livebytes.
+ * A run may have at most RF_LIVE_MAX_ROWS rows (nlive_est): RF_EINVAL beyond,
+ * the object left usable.  A run that fails after its walk (that refusal, or
+ * RF_EDEVICE) keeps the previous run's filter, statistics and maxlivebytes;
+ * the states and lists are then undefined until the next run that succeeds.  Replaced and cleared values leave their rows stale
+ * in the arena until close (stale_rows); there is no compaction. */
+typedef struct rf_liveset rf_liveset;
+#define RF_LIVE_UNSEEN 0
+#define RF_LIVE_WALKED 1
+#define RF_LIVE_VALUE 2
+#define RF_LIVE_MAX_ROWS 1073741824 /* 2^30 rows per run: the dedup table indexes rows with 32 bits */
+#define RF_LIVE_LIST_TILE 1024      /* nodes per tile of the list's mark / scan / scatter */
+#define RF_LIVE_ROUND_BATCH 4       /* walk rounds enqueued between two host reads */
+typedef struct {
+    uint64_t n_nodes, counts[3];     /* nodes per state after the last run */
+    uint64_t contributions;          /* frontier values + writer entries */
+    uint64_t nlive_est, nlive;       /* eval.go:813-814 and :856 */
+    int64_t livebytes, maxlivebytes;
+    uint64_t m, k;
+    uint32_t rounds, changed;        /* rounds: round launches enqueued, in batches of RF_LIVE_ROUND_BATCH
+                                        (trailing ones may have found an empty frontier); <= the depth bound */
+    uint64_t arena_rows, stale_rows; /* rows stored; rows of replaced / cleared values */
+    uint64_t device_bytes;
+} rf_liveset_stats;
+/* bloom.EstimateParameters (bloom.go:120-124) in double, on the host alone:
+ * m = ceil(-n ln p / ln^2 2), k = ceil(ln 2 * m / n).  RF_EINVAL for n = 0 or
+ * p outside (0, 1). */
+int rf_bloom_estimate(uint64_t n, double p, uint64_t *m, uint64_t *k);
+int rf_liveset_open(rf_ctx *ctx, uint64_t n, const uint64_t *edge_ptr, const uint32_t *edges, rf_liveset **out);
+void rf_liveset_close(rf_liveset *l);
+/* nodes[i] now has the value rows [sum(counts[0..i)), +counts[i]) of ids32 /
+ * sizes; it replaces an older one (a node listed twice keeps its last).
+ * RF_EINVAL for a node >= n or a row total that overflows.  The device form
+ * reads the rows from device memory on `stream` and returns when they are
+ * stored.  A call that fails changes no value. */
+int rf_liveset_set_values(rf_liveset *l, const uint32_t *nodes, const uint32_t *counts, uint64_t n_nodes,
+                          const uint8_t *ids32, const int64_t *sizes);
+int rf_liveset_set_values_device(rf_liveset *l, const uint32_t *nodes, const uint32_t *counts, uint64_t n_nodes,
+                                 const void *d_ids32, const void *d_sizes, void *stream);
+/* These nodes are no longer FlowDone: they have no value. */
+int rf_liveset_clear_values(rf_liveset *l, const uint32_t *nodes, uint64_t n_nodes);
+/* One collection (roots, writers: host arrays; duplicates as above).  Holds
+ * the context's lock and returns when the filter is complete. */
+int rf_liveset_run(rf_liveset *l, const uint32_t *roots, uint64_t n_roots, const uint32_t *writers,
+                   uint64_t n_writers, void *stream);
+/* The last run's filter, borrowed: valid until the next run or close, for
+ * every rf_bloom_* call that reads a filter (probe, collect, params, words,
+ * the marshalers, and as the liveset of a plan or feed lookup);
+ * rf_bloom_destroy on it is a no-op.  RF_EPRECONDITION before the first run. */
+int rf_liveset_filter(rf_liveset *l, rf_bloom **b);
+/* Results of the last run: one RF_LIVE_* byte per node; the nodes in `state`,
+ * strictly ascending, with the cap rule of rf_eval_plan_list. */
+int rf_liveset_states(rf_liveset *l, uint8_t *state);
+int rf_liveset_list(rf_liveset *l, int state, uint64_t cap, uint32_t *nodes, uint64_t *found);
+/* size = sizeof(rf_liveset_stats) of the caller's header. */
+int rf_liveset_stats_get(rf_liveset *l, rf_liveset_stats *out, uint64_t size);
+
 /* ---- K4: bloomlive / assoc probe (bloom.go:182-190, bloomlive.go:30-36) --
  * Filters cache-key lookups before Assoc.Get (eval.go:1202-1220) and serves
  * Liveset.Contains for Repository.Collect (repository/file/repository.go:304-327). */

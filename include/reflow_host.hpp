@@ -572,6 +572,7 @@ class Liveset {
    private:
     friend class Eval;      // (FeedLookup)
     friend class EvalPlan;  // (Run / Reject)
+    friend class GcLiveset; // (Collect lends its filter)
     explicit Liveset(rf_bloom* b) : b_(b) {}
     rf_bloom* b_ = nullptr;
 };
@@ -675,6 +676,39 @@ class EvalPlan {
    private:
     rf_eval_plan* p_ = nullptr;
     uint64_t n_keys_ = 0;
+};
+
+// Eval.collect (eval.go:791-868) for a whole Flow graph, on the device
+// (rf_liveset_*): the walk from the roots down to the first completed values,
+// the writers' values, the per-value Files() dedup and the bloom filter that
+// Repository.Collect takes.  Nodes are numbered by the caller: node i's edges
+// are edges[edge_ptr[i] .. edge_ptr[i+1]) -- its Deps, and for an OpMap its
+// MapFlow.  Opened once, values set as nodes finish, Collect once per GC.
+class GcLiveset {
+   public:
+    GcLiveset(Engine& e, const std::vector<uint64_t>& edge_ptr, const std::vector<uint32_t>& edges);
+    ~GcLiveset();
+    GcLiveset(const GcLiveset&) = delete;
+    GcLiveset& operator=(const GcLiveset&) = delete;
+    // nodes[i] is FlowDone with the Fileset *vals[i] (its Map entries, List
+    // flattened: Fileset.N() rows); an older value is replaced.
+    void SetValues(const std::vector<uint32_t>& nodes, const std::vector<const Fileset*>& vals);
+    void SetValue(uint32_t node, const Fileset& v) { SetValues({node}, {&v}); }
+    void ClearValues(const std::vector<uint32_t>& nodes);  // no longer FlowDone
+    struct Result {
+        bool changed;       // eval.go:862: Repository.Collect is due
+        uint64_t nlive;     // eval.go:856
+        int64_t livebytes;  // eval.go:854
+        Liveset& live;      // borrowed: valid until the next Collect
+    };
+    Result Collect(const std::vector<uint32_t>& roots, const std::vector<uint32_t>& writers = {});
+    std::vector<uint8_t> States();          // one RF_LIVE_* per node
+    std::vector<uint32_t> List(int state);  // ascending node ids
+    rf_liveset_stats Stats();
+
+   private:
+    rf_liveset* l_ = nullptr;
+    Liveset live_{nullptr};  // the object's own filter (rf_bloom_destroy leaves it alone)
 };
 
 }  // namespace reflow

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
@@ -32,6 +33,11 @@ FEED_TILE_SLOTS = 8192
 RF_PLAN_F_CACHEABLE, RF_PLAN_F_EXTERN, RF_PLAN_F_INVALID, RF_PLAN_F_DONE = 1, 2, 4, 8
 RF_PLAN_UNSEEN, RF_PLAN_TODO, RF_PLAN_READY, RF_PLAN_HIT, RF_PLAN_DONE = range(5)
 RF_PLAN_MAX_KEYS = 8
+# GC liveset (rf_liveset_*): node states, rows per run, nodes per list tile, rounds per host read
+RF_LIVE_UNSEEN, RF_LIVE_WALKED, RF_LIVE_VALUE = range(3)
+RF_LIVE_MAX_ROWS = 1 << 30
+RF_LIVE_LIST_TILE = 1024
+RF_LIVE_ROUND_BATCH = 4
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -72,6 +78,9 @@ EXPORTS = [
     "rf_eval_plan_run", "rf_eval_plan_run_host", "rf_eval_plan_reject", "rf_eval_plan_reject_host",
     "rf_eval_plan_states", "rf_eval_plan_states_device", "rf_eval_plan_list", "rf_eval_plan_list_device",
     "rf_eval_plan_stats_get",
+    "rf_bloom_estimate", "rf_liveset_open", "rf_liveset_close", "rf_liveset_set_values",
+    "rf_liveset_set_values_device", "rf_liveset_clear_values", "rf_liveset_run", "rf_liveset_filter",
+    "rf_liveset_states", "rf_liveset_list", "rf_liveset_stats_get",
 ]
 
 
@@ -277,6 +286,15 @@ class EvalPlanStats(ctypes.Structure):
                 ("device_bytes", ctypes.c_uint64)]
 
 
+class LivesetStats(ctypes.Structure):
+    """rf_liveset_stats: the figures of the last run (arena_rows / stale_rows: as of now)."""
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("counts", ctypes.c_uint64 * 3), ("contributions", ctypes.c_uint64),
+                ("nlive_est", ctypes.c_uint64), ("nlive", ctypes.c_uint64), ("livebytes", ctypes.c_int64),
+                ("maxlivebytes", ctypes.c_int64), ("m", ctypes.c_uint64), ("k", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint32), ("changed", ctypes.c_uint32), ("arena_rows", ctypes.c_uint64),
+                ("stale_rows", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -434,6 +452,15 @@ def lib():
             "rf_eval_plan_list": ([vp, i32, u64, vp, vp, vp, vp, vp], i32),
             "rf_eval_plan_list_device": ([vp, i32, u64, vp, vp, vp, vp, vp, vp], i32),
             "rf_eval_plan_stats_get": ([vp, vp, u64], i32),
+            "rf_bloom_estimate": ([u64, ctypes.c_double, vp, vp], i32),
+            "rf_liveset_open": ([vp, u64, vp, vp, vp], i32), "rf_liveset_close": ([vp], None),
+            "rf_liveset_set_values": ([vp, vp, vp, u64, vp, vp], i32),
+            "rf_liveset_set_values_device": ([vp, vp, vp, u64, vp, vp, vp], i32),
+            "rf_liveset_clear_values": ([vp, vp, u64], i32),
+            "rf_liveset_run": ([vp, vp, u64, vp, u64, vp], i32),
+            "rf_liveset_filter": ([vp, vp], i32), "rf_liveset_states": ([vp, vp], i32),
+            "rf_liveset_list": ([vp, i32, u64, vp, vp], i32),
+            "rf_liveset_stats_get": ([vp, vp, u64], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -1023,9 +1050,10 @@ class Graph:
 class Bloom:
     """rf_bloom: device-resident willf/bloom filter with bloomlive semantics."""
 
-    def __init__(self, ctx: Context, handle):
+    def __init__(self, ctx: Context, handle, owned=True):
         self.ctx = ctx
         self._h = handle
+        self._owned = owned  # False: borrowed (GcLiveset.filter): never destroyed from here
 
     @classmethod
     def load(cls, ctx, m, k, words: np.ndarray, length):
@@ -1113,9 +1141,9 @@ class Bloom:
         _check(lib().rf_bloom_collect_device(self._h, d_digests, d_sizes, n, d_dead_idx, d_counts2, stream))
 
     def close(self):
-        if self._h:
+        if self._h and self._owned:
             lib().rf_bloom_destroy(self._h)
-            self._h = ctypes.c_void_p()
+        self._h = ctypes.c_void_p()
 
     def __del__(self):
         try:
@@ -1454,6 +1482,119 @@ class EvalPlan:
     def close(self):
         if self._h:
             lib().rf_eval_plan_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bloom_estimate(n: int, p: float):
+    """rf_bloom_estimate (host only): bloom.EstimateParameters -> (m, k)."""
+    m, k = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().rf_bloom_estimate(n, p, ctypes.byref(m), ctypes.byref(k)))
+    return m.value, k.value
+
+
+class GcLiveset:
+    """rf_liveset: Eval.collect's walk, dedup and filter build on the device.
+    edge_ptr / edges: the nodes' Deps (an OpMap's MapFlow appended) in CSR
+    form.  Values are set as nodes finish; run() is one collection."""
+
+    def __init__(self, ctx: Context, edge_ptr, edges):
+        self.ctx = ctx
+        ep = np.ascontiguousarray(edge_ptr, dtype=np.uint64)
+        ed = np.ascontiguousarray(edges, dtype=np.uint32)
+        self.n = max(len(ep) - 1, 0)
+        self._h = ctypes.c_void_p()
+        self._lent = []  # weak references to the Blooms filter() handed out
+        _check(lib().rf_liveset_open(ctx.handle, self.n, _ptr(ep) if self.n else None, _ptr(ed) if len(ed) else None,
+                                     ctypes.byref(self._h)))
+
+    @staticmethod
+    def _lists(nodes, counts):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        ct = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert len(nd) == len(ct)
+        return nd, ct
+
+    def set_values(self, nodes, counts, ids32, sizes):
+        """nodes[i] gets the next counts[i] rows of ids32 [rows, 32] / sizes [rows]."""
+        nd, ct = self._lists(nodes, counts)
+        ids = np.ascontiguousarray(ids32, dtype=np.uint8).reshape(-1)
+        sz = np.ascontiguousarray(sizes, dtype=np.int64)
+        assert len(ids) == 32 * len(sz) and len(sz) == int(ct.sum(dtype=np.uint64))
+        _check(lib().rf_liveset_set_values(self._h, _ptr(nd) if len(nd) else None, _ptr(ct) if len(ct) else None,
+                                           len(nd), _ptr(ids) if len(ids) else None, _ptr(sz) if len(sz) else None))
+
+    def set_values_device(self, nodes, counts, d_ids32, d_sizes, stream=None):
+        nd, ct = self._lists(nodes, counts)
+        _check(lib().rf_liveset_set_values_device(self._h, _ptr(nd) if len(nd) else None,
+                                                  _ptr(ct) if len(ct) else None, len(nd), d_ids32, d_sizes, stream))
+
+    def clear_values(self, nodes):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        _check(lib().rf_liveset_clear_values(self._h, _ptr(nd) if len(nd) else None, len(nd)))
+
+    def run(self, roots, writers=(), stream=None) -> "LivesetStats":
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        w = np.ascontiguousarray(writers, dtype=np.uint32)
+        _check(lib().rf_liveset_run(self._h, _ptr(r) if len(r) else None, len(r), _ptr(w) if len(w) else None,
+                                    len(w), stream))
+        return self.stats()
+
+    def filter(self) -> "Bloom":
+        """The last run's filter, borrowed: valid until the next run or close
+        (closing the returned Bloom only drops the handle; close() here
+        drops the handles of every Bloom handed out)."""
+        h = ctypes.c_void_p()
+        _check(lib().rf_liveset_filter(self._h, ctypes.byref(h)))
+        b = Bloom(self.ctx, h, owned=False)
+        self._lent = [r for r in self._lent if r() is not None] + [weakref.ref(b)]
+        return b
+
+    def states(self) -> np.ndarray:
+        out = np.zeros(max(self.n, 1), dtype=np.uint8)
+        _check(lib().rf_liveset_states(self._h, _ptr(out)))
+        return out[:self.n]
+
+    def count(self, state) -> int:
+        n = ctypes.c_uint64()
+        rc = lib().rf_liveset_list(self._h, state, 0, None, ctypes.byref(n))
+        if rc != RF_OK and not (rc == RF_EINVAL and n.value):
+            _check(rc)
+        return n.value
+
+    def list(self, state, cap=None, poison=None) -> np.ndarray:
+        """rf_liveset_list: the nodes in `state`, ascending.  cap: the buffer's
+        rows (default: the count); RfError(RF_EINVAL) with .needed and .buffer
+        when short."""
+        cap = self.count(state) if cap is None else int(cap)
+        nodes = np.full(max(cap, 1), (0 if poison is None else poison) * 0x01010101, dtype=np.uint32)
+        n = ctypes.c_uint64()
+        rc = lib().rf_liveset_list(self._h, state, cap, _ptr(nodes), ctypes.byref(n))
+        if rc != RF_OK:
+            err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+            err.needed = n.value
+            err.buffer = nodes
+            raise err
+        return nodes[:n.value]
+
+    def stats(self) -> LivesetStats:
+        s = LivesetStats()
+        _check(lib().rf_liveset_stats_get(self._h, ctypes.byref(s), ctypes.sizeof(s)))
+        return s
+
+    def close(self):
+        for r in getattr(self, "_lent", []):  # the filters die with the object
+            b = r()
+            if b is not None:
+                b._h = ctypes.c_void_p()
+        self._lent = []
+        if self._h:
+            lib().rf_liveset_close(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

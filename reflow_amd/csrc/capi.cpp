@@ -41,6 +41,7 @@
 #include "host_par.h"
 #include "host_sha.h"
 #include "plan_internal.h"
+#include "live_internal.h"
 #include "reflow_hip.h"
 #include "walk.h"
 #include "wire.h"
@@ -2614,6 +2615,8 @@ struct rf_bloom {
     rf_ctx* ctx = nullptr;
     BloomDev b;
     DevBuf words, len_dev, keys, out, sizes, dead, tiles, idx, nb;
+    bool lent = false;      // owned by an rf_liveset (rf_liveset_filter): rf_bloom_destroy leaves it alone
+    uint64_t len_host = 0;  // (lent) the length as last uploaded
 };
 
 static int bloom_make(rf_ctx* ctx, uint64_t m, uint64_t k, const uint64_t* words, uint64_t nwords,
@@ -2674,13 +2677,53 @@ extern "C" int rf_bloom_load_json(rf_ctx* ctx, const char* json, size_t len, rf_
     return rc ? rc : bloom_make(ctx, m, k, w.data(), w.size(), length, out);
 }
 
-extern "C" void rf_bloom_destroy(rf_bloom* bl) {
-    if (!bl) return;
-    DevGuard dg(bl->ctx->device);
+static void bloom_release(rf_bloom* bl) {
     bl->words.release();
     bl->len_dev.release();
     for (DevBuf* d : {&bl->keys, &bl->out, &bl->sizes, &bl->dead, &bl->tiles, &bl->idx, &bl->nb}) d->release();
     delete bl;
+}
+
+// ---- filters an rf_liveset owns and lends out (live_internal.h) ----------------
+int rf::bloom_lent_shape(rf_ctx* ctx, rf_bloom** slot, uint64_t m, uint64_t k, hipStream_t s) {
+    ARG(m >= 1 && k >= 1 && k < (1ull << 31), "bloom parameters out of range");
+    if (!*slot) {
+        *slot = new rf_bloom();
+        (*slot)->ctx = ctx;
+        (*slot)->lent = true;
+    }
+    rf_bloom* bl = *slot;
+    const uint64_t cap = std::max<uint64_t>((m + 63) / 64, 1);
+    hipError_t e;
+    if ((e = bl->words.ensure(8 * cap)) != hipSuccess || (e = bl->len_dev.ensure(8)) != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? RF_ENOMEM : RF_EDEVICE, "bloom alloc: %s", hipGetErrorString(e));
+    bl->len_host = m;  // bloom.New: bitset.New(m)
+    HIPC(hipMemsetAsync(bl->words.p, 0, 8 * cap, s));
+    HIPC(hipMemcpyAsync(bl->len_dev.p, &bl->len_host, 8, hipMemcpyHostToDevice, s));
+    bl->b.m = m;
+    bl->b.k = k;
+    bl->b.length = m;
+    bl->b.nwords = cap;
+    bl->b.words = bl->words.as<uint64_t>();
+    bl->b.len_dev = bl->len_dev.as<uint64_t>();
+    return RF_OK;
+}
+
+void rf::bloom_lent_free(rf_bloom* bl) {
+    if (bl) bloom_release(bl);
+}
+
+uint64_t rf::bloom_device_bytes(rf_bloom* bl) {
+    if (!bl) return 0;
+    uint64_t t = bl->words.cap + bl->len_dev.cap;
+    for (const DevBuf* d : {&bl->keys, &bl->out, &bl->sizes, &bl->dead, &bl->tiles, &bl->idx, &bl->nb}) t += d->cap;
+    return t;
+}
+
+extern "C" void rf_bloom_destroy(rf_bloom* bl) {
+    if (!bl || bl->lent) return;  // a lent filter belongs to its rf_liveset
+    DevGuard dg(bl->ctx->device);
+    bloom_release(bl);
 }
 
 extern "C" int rf_bloom_probe_device(rf_bloom* bl, const void* d_digests32, uint64_t n, void* d_out,

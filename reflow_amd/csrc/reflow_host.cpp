@@ -1402,4 +1402,72 @@ rf_eval_plan_stats EvalPlan::Stats() {
     return st;
 }
 
+// ---- GC liveset -------------------------------------------------------------------
+GcLiveset::GcLiveset(Engine& e, const std::vector<uint64_t>& edge_ptr, const std::vector<uint32_t>& edges) {
+    if (edge_ptr.empty() || edge_ptr.back() != edges.size())
+        throw Error(RF_EINVAL, "GcLiveset: edge_ptr needs n + 1 entries ending at the edge count");
+    reflow::Check(rf_liveset_open(e.ctx(), edge_ptr.size() - 1, edge_ptr.data(), edges.data(), &l_));
+}
+
+GcLiveset::~GcLiveset() {
+    live_.b_ = nullptr;
+    rf_liveset_close(l_);
+}
+
+static void flatten_rows(const Fileset& v, std::vector<Digest>& ids, std::vector<int64_t>& sizes) {
+    if (v.List)
+        for (const Fileset& c : *v.List) flatten_rows(c, ids, sizes);
+    for (const auto& kv : v.Map) {
+        ids.push_back(kv.second.ID);
+        sizes.push_back(kv.second.Size);
+    }
+}
+
+void GcLiveset::SetValues(const std::vector<uint32_t>& nodes, const std::vector<const Fileset*>& vals) {
+    if (nodes.size() != vals.size()) throw Error(RF_EINVAL, "GcLiveset: one value per node");
+    std::vector<uint32_t> counts;
+    std::vector<Digest> ids;
+    std::vector<int64_t> sizes;
+    for (const Fileset* v : vals) {
+        const size_t before = ids.size();
+        flatten_rows(*v, ids, sizes);
+        counts.push_back((uint32_t)(ids.size() - before));
+    }
+    reflow::Check(rf_liveset_set_values(l_, nodes.data(), counts.data(), nodes.size(),
+                                        ids.empty() ? nullptr : ids[0].b.data(), sizes.data()));
+}
+
+void GcLiveset::ClearValues(const std::vector<uint32_t>& nodes) {
+    reflow::Check(rf_liveset_clear_values(l_, nodes.data(), nodes.size()));
+}
+
+GcLiveset::Result GcLiveset::Collect(const std::vector<uint32_t>& roots, const std::vector<uint32_t>& writers) {
+    reflow::Check(rf_liveset_run(l_, roots.data(), roots.size(), writers.data(), writers.size(), nullptr));
+    reflow::Check(rf_liveset_filter(l_, &live_.b_));
+    const rf_liveset_stats st = Stats();
+    return Result{st.changed != 0, st.nlive, st.livebytes, live_};
+}
+
+std::vector<uint8_t> GcLiveset::States() {
+    const rf_liveset_stats st = Stats();
+    std::vector<uint8_t> out(st.n_nodes);
+    if (st.n_nodes) reflow::Check(rf_liveset_states(l_, out.data()));
+    return out;
+}
+
+std::vector<uint32_t> GcLiveset::List(int state) {
+    const rf_liveset_stats st = Stats();
+    std::vector<uint32_t> out(st.n_nodes + 1);
+    uint64_t found = 0;
+    reflow::Check(rf_liveset_list(l_, state, st.n_nodes, out.data(), &found));
+    out.resize(found);
+    return out;
+}
+
+rf_liveset_stats GcLiveset::Stats() {
+    rf_liveset_stats st;
+    reflow::Check(rf_liveset_stats_get(l_, &st, sizeof st));
+    return st;
+}
+
 }  // namespace reflow
