@@ -996,6 +996,114 @@ int rf_assoc_file_format(const int32_t *kinds, const uint8_t *keys32, const uint
 int rf_assoc_file_parse(const uint8_t *buf, uint64_t len, int32_t *kinds, uint8_t *keys32, uint8_t *vals32,
                         uint64_t cap_entries, uint64_t *n);
 
+/* ---- Repository index in HBM: batched Stat, missing() and NeedTransfer ------
+ * What a repository holds, as a set of object IDs with their sizes on the
+ * device: the object map of the in-memory repository
+ * (test/testutil/repository.go:25-115) and file.Repository.Stat
+ * (repository/file/repository.go:93-101).  Against it run, for batches of
+ * Fileset values, Eval.lookup's missing() (eval.go:1227-1243, 1983-2014) and
+ * Manager.NeedTransfer (repository/manager.go:197-234; eval.go:412-444,
+ * 1273-1282) -- one Repository.Stat goroutine per file in the reference, whose
+ * own comment asks for a batch stat call -- and Repository.Collect
+ * (repository/file/repository.go:304-327) on the index itself.
+ * Table: open addressing, one slot = tag word, 32-B ID, int64 size; a removed
+ * object leaves a tombstone.  Slots: the smallest power of two >=
+ * max(RF_REPO_MIN_SLOTS, 2 * capacity), capacity <= 2^30.  Before a Put batch
+ * of n rows the host compares live + tombstones + n with half the slots: beyond
+ * it the table is rebuilt without its tombstones at twice the slots (doubled
+ * again until live + n fit in half).  Probing is bounded (65536 slots at load
+ * <= 1/2: not reachable for SHA-256 IDs); a call that hits the bound fails
+ * with RF_EDEVICE, and so does every later call on the object (fail-stop; an
+ * asynchronous device form reports it through the next call).  Every call
+ * holds the context's lock; what a device form leaves on its stream is waited
+ * for by the next call on the object.
+ *
+ * Put (content addressing: an ID determines its size): status[i] = RF_OK when
+ * the ID is new, or present with the same size; RF_EINTEGRITY when the index,
+ * or a row of the same batch with a lower index, gives the ID another size --
+ * the stored size then stays as it was (first wins by row index, the same on
+ * every run).  A negative size: the host form refuses the whole batch with
+ * RF_EINVAL and changes nothing, the device form sets RF_EINVAL on that row,
+ * which then takes no part.  A removed ID that is Put again is a fresh object
+ * of any size.  remove: removed[i] = 1 for the first row of an ID the index
+ * held, else 0.  stat: the size, or -1 (NotExist).  The device forms of put and
+ * remove return when applied; stat_device is asynchronous on `stream`.
+ *
+ * collect: every object whose WD(ID) `live` does not contain is removed;
+ * *removed their number, *removed_bytes the sum of their sizes (either may be
+ * NULL).  live = NULL removes everything, as the reference does with a nil
+ * liveset.  A filter borrowed from rf_liveset_filter is accepted.  Returns
+ * when done.
+ *
+ * missing / need_transfer: the work comes in GROUPS of (ID, Size) rows, group
+ * g's rows following group g-1's, counts[g] of them (the layout
+ * rf_liveset_set_values takes; zero rows is valid).  Per group: Files(), the
+ * distinct (ID, Size) pairs (executor.go:82-92, 116-125; no dedup across
+ * groups), each then looked up by ID (two rows with one ID and two sizes are
+ * two files, and both are missing or neither).  need_transfer: group g is
+ * Fileset{List: deps' values} of nodes[g] -- the value rows of its edges in
+ * the liveset's CSR, in edge order (an edge listed twice contributes twice; an
+ * OpMap's appended MapFlow edge is the caller's concern).  An edge whose node
+ * has no value: status[g] = RF_EPRECONDITION and zero counts for that group
+ * alone; the device form gives a node >= n status RF_EINVAL likewise (the host
+ * form refuses the call).  Both objects of one context (RF_EINVAL).
+ * The list: the distinct missing files, by group ascending and within a group
+ * by the row of their first occurrence ascending (over the concatenated rows
+ * one global ascending order, equal bytes from run to run); miss_ptr[g] = the
+ * first list entry of group g.  If any of miss_rows / miss_ids32 / miss_sizes
+ * is given the cap rule of rf_eval_plan_list holds: nothing at or beyond cap is
+ * written, *n_listed is set either way, and the host form returns RF_EINVAL
+ * when the total exceeds cap (the device form's caller compares).
+ * At most RF_REPO_MAX_ROWS rows per call: RF_EINVAL beyond, the object left
+ * usable.  The calls read the row total back once (need_transfer: and the
+ * edge total); the rest is asynchronous on `stream` in the device forms. */
+typedef struct rf_repo rf_repo;
+#define RF_REPO_MAX_ROWS 1073741824 /* 2^30 rows per call: the dedup table indexes rows with 32 bits */
+#define RF_REPO_MIN_SLOTS 1024      /* the smallest table */
+#define RF_REPO_LIST_TILE 1024      /* rows per tile of the list's mark / scan / scatter */
+typedef struct {
+    uint64_t objects;    /* live objects */
+    int64_t bytes;       /* the sum of their sizes */
+    uint64_t tombstones; /* removed objects that still hold a slot */
+    uint64_t capacity;   /* slots */
+    uint64_t rebuilds;   /* growths so far */
+    uint64_t device_bytes;
+    uint64_t last_rows, last_files, last_missing; /* the last missing / need_transfer call: rows, distinct
+                                                     files over its groups, those not in the index */
+} rf_repo_stats;
+typedef struct {            /* every pointer may be NULL; host pointers in the host forms, device in the device forms */
+    uint32_t *n_files;      /* [n_groups] distinct (ID, Size) */
+    uint32_t *n_missing;    /* [n_groups] of those, ID not in the index */
+    int64_t  *missing_bytes;/* [n_groups] sum of their sizes: lookup's message (eval.go:1236-1242), TransferSize (eval.go:429-436) */
+    int32_t  *status;       /* [n_groups] need_transfer only */
+    uint64_t  cap;          /* capacity of the three list arrays */
+    uint64_t *miss_ptr;     /* [n_groups + 1] exclusive scan of n_missing */
+    uint64_t *miss_rows;    /* row form only: input row of each missing file's first occurrence */
+    uint8_t  *miss_ids32;   /* its ID */
+    int64_t  *miss_sizes;   /* its size */
+    uint64_t *n_listed;     /* total missing, written whether it fits or not */
+} rf_repo_missing_out;
+int rf_repo_new(rf_ctx *ctx, uint64_t capacity, rf_repo **out);
+void rf_repo_destroy(rf_repo *r);
+int rf_repo_put(rf_repo *r, const uint8_t *ids32, const int64_t *sizes, uint64_t n, int32_t *status);
+int rf_repo_put_device(rf_repo *r, const void *d_ids32, const void *d_sizes, uint64_t n, void *d_status,
+                       void *stream);
+int rf_repo_remove(rf_repo *r, const uint8_t *ids32, uint64_t n, uint8_t *removed);
+int rf_repo_remove_device(rf_repo *r, const void *d_ids32, uint64_t n, void *d_removed, void *stream);
+int rf_repo_stat(rf_repo *r, const uint8_t *ids32, uint64_t n, int64_t *sizes);
+int rf_repo_stat_device(rf_repo *r, const void *d_ids32, uint64_t n, void *d_sizes, void *stream);
+int rf_repo_collect(rf_repo *r, rf_bloom *live, uint64_t *removed, int64_t *removed_bytes, void *stream);
+/* size = sizeof(rf_repo_stats) of the caller's header. */
+int rf_repo_stats_get(rf_repo *r, rf_repo_stats *out, uint64_t size);
+int rf_repo_missing(rf_repo *r, const uint32_t *counts, uint64_t n_groups, const uint8_t *ids32,
+                    const int64_t *sizes, rf_repo_missing_out *o);
+int rf_repo_missing_device(rf_repo *r, const void *d_counts, uint64_t n_groups, const void *d_ids32,
+                           const void *d_sizes, uint64_t n_rows, rf_repo_missing_out *o, void *stream);
+int rf_repo_need_transfer(rf_repo *r, rf_liveset *l, const uint32_t *nodes, uint64_t n_nodes,
+                          rf_repo_missing_out *o);
+int rf_repo_need_transfer_device(rf_repo *r, rf_liveset *l, const void *d_nodes, uint64_t n_nodes,
+                                 rf_repo_missing_out *o, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -573,6 +573,7 @@ class Liveset {
     friend class Eval;      // (FeedLookup)
     friend class EvalPlan;  // (Run / Reject)
     friend class GcLiveset; // (Collect lends its filter)
+    friend class RepoIndex; // (Collect reads it)
     explicit Liveset(rf_bloom* b) : b_(b) {}
     rf_bloom* b_ = nullptr;
 };
@@ -707,8 +708,48 @@ class GcLiveset {
     rf_liveset_stats Stats();
 
    private:
+    friend class RepoIndex;  // (NeedTransfer reads its values, Collect its filter)
     rf_liveset* l_ = nullptr;
     Liveset live_{nullptr};  // the object's own filter (rf_bloom_destroy leaves it alone)
+};
+
+// What a repository holds, on the device (rf_repo_*): the object map of the
+// in-memory repository (test/testutil/repository.go:25-115) with batched Stat,
+// Eval.lookup's missing() (eval.go:1227-1243) and Manager.NeedTransfer
+// (repository/manager.go:197-234) for batches of values, and
+// Repository.Collect on the index itself.
+class RepoIndex {
+   public:
+    explicit RepoIndex(Engine& e, uint64_t capacity = 1024);
+    ~RepoIndex();
+    RepoIndex(const RepoIndex&) = delete;
+    RepoIndex& operator=(const RepoIndex&) = delete;
+    // status per row: RF_OK, or RF_EINTEGRITY for an ID that has another size already
+    std::vector<int> Put(const std::vector<Digest>& ids, const std::vector<int64_t>& sizes);
+    std::vector<int64_t> Stat(const std::vector<Digest>& ids);  // -1 = NotExist
+    std::vector<bool> Remove(const std::vector<Digest>& ids);
+    // Repository.Collect with the last GcLiveset::Collect's filter: (objects removed, their bytes)
+    std::pair<uint64_t, int64_t> Collect(const GcLiveset& live);
+    std::pair<uint64_t, int64_t> CollectAll();  // a nil liveset: everything goes
+    struct Report {
+        std::vector<uint32_t> n_files, n_missing;  // per group
+        std::vector<int64_t> missing_bytes;
+        std::vector<int> status;                   // NeedTransfer only
+        std::vector<uint64_t> miss_ptr;            // [groups + 1] into the three lists
+        std::vector<uint64_t> miss_rows;           // Missing only: flattened row of the first occurrence
+        std::vector<File> files;                   // the distinct missing files, group by group
+    };
+    // One group per value (its Map entries, List flattened, as GcLiveset's values).
+    Report Missing(const std::vector<const Fileset*>& vals);
+    Report Missing(const std::vector<Fileset>& vals);
+    // Group g = Fileset{List: the values of nodes[g]'s deps}.  The list's size is not known before the
+    // call (nodes may repeat, deps share values), so this runs the device sequence twice: once to count,
+    // once to list.  A caller that can bound the list calls rf_repo_need_transfer itself, once.
+    Report NeedTransfer(GcLiveset& l, const std::vector<uint32_t>& nodes);
+    rf_repo_stats Stats();
+
+   private:
+    rf_repo* r_ = nullptr;
 };
 
 }  // namespace reflow

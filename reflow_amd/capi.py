@@ -38,6 +38,10 @@ RF_LIVE_UNSEEN, RF_LIVE_WALKED, RF_LIVE_VALUE = range(3)
 RF_LIVE_MAX_ROWS = 1 << 30
 RF_LIVE_LIST_TILE = 1024
 RF_LIVE_ROUND_BATCH = 4
+# repository index (rf_repo_*): rows per call, the smallest table, rows per list tile
+RF_REPO_MAX_ROWS = 1 << 30
+RF_REPO_MIN_SLOTS = 1024
+RF_REPO_LIST_TILE = 1024
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -81,6 +85,9 @@ EXPORTS = [
     "rf_bloom_estimate", "rf_liveset_open", "rf_liveset_close", "rf_liveset_set_values",
     "rf_liveset_set_values_device", "rf_liveset_clear_values", "rf_liveset_run", "rf_liveset_filter",
     "rf_liveset_states", "rf_liveset_list", "rf_liveset_stats_get",
+    "rf_repo_new", "rf_repo_destroy", "rf_repo_put", "rf_repo_put_device", "rf_repo_remove",
+    "rf_repo_remove_device", "rf_repo_stat", "rf_repo_stat_device", "rf_repo_collect", "rf_repo_stats_get",
+    "rf_repo_missing", "rf_repo_missing_device", "rf_repo_need_transfer", "rf_repo_need_transfer_device",
 ]
 
 
@@ -295,6 +302,21 @@ class LivesetStats(ctypes.Structure):
                 ("stale_rows", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
 
 
+class RepoStats(ctypes.Structure):
+    """rf_repo_stats: the index as of now, and the last missing / need_transfer call's totals."""
+    _fields_ = [("objects", ctypes.c_uint64), ("bytes", ctypes.c_int64), ("tombstones", ctypes.c_uint64),
+                ("capacity", ctypes.c_uint64), ("rebuilds", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
+                ("last_rows", ctypes.c_uint64), ("last_files", ctypes.c_uint64), ("last_missing", ctypes.c_uint64)]
+
+
+class RepoMissingOut(ctypes.Structure):
+    """rf_repo_missing_out: host pointers in the host forms, device pointers in the device forms."""
+    _fields_ = [("n_files", ctypes.c_void_p), ("n_missing", ctypes.c_void_p), ("missing_bytes", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("cap", ctypes.c_uint64), ("miss_ptr", ctypes.c_void_p),
+                ("miss_rows", ctypes.c_void_p), ("miss_ids32", ctypes.c_void_p), ("miss_sizes", ctypes.c_void_p),
+                ("n_listed", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -461,6 +483,15 @@ def lib():
             "rf_liveset_filter": ([vp, vp], i32), "rf_liveset_states": ([vp, vp], i32),
             "rf_liveset_list": ([vp, i32, u64, vp, vp], i32),
             "rf_liveset_stats_get": ([vp, vp, u64], i32),
+            "rf_repo_new": ([vp, u64, vp], i32), "rf_repo_destroy": ([vp], None),
+            "rf_repo_put": ([vp, vp, vp, u64, vp], i32), "rf_repo_put_device": ([vp, vp, vp, u64, vp, vp], i32),
+            "rf_repo_remove": ([vp, vp, u64, vp], i32), "rf_repo_remove_device": ([vp, vp, u64, vp, vp], i32),
+            "rf_repo_stat": ([vp, vp, u64, vp], i32), "rf_repo_stat_device": ([vp, vp, u64, vp, vp], i32),
+            "rf_repo_collect": ([vp, vp, vp, vp, vp], i32), "rf_repo_stats_get": ([vp, vp, u64], i32),
+            "rf_repo_missing": ([vp, vp, u64, vp, vp, vp], i32),
+            "rf_repo_missing_device": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
+            "rf_repo_need_transfer": ([vp, vp, vp, u64, vp], i32),
+            "rf_repo_need_transfer_device": ([vp, vp, vp, u64, vp, vp], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -1595,6 +1626,150 @@ class GcLiveset:
         self._lent = []
         if self._h:
             lib().rf_liveset_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RepoMissing:
+    """What Repo.missing / Repo.need_transfer return: per-group arrays, the
+    list of distinct missing files (group by group, first occurrence
+    ascending) and n_listed, the total whether the list fitted or not."""
+
+    FIELDS = ("n_files", "n_missing", "missing_bytes", "status", "miss_ptr", "miss_rows", "miss_ids32", "miss_sizes",
+              "n_listed")
+
+    def __init__(self):
+        for f in self.FIELDS:
+            setattr(self, f, None)
+
+
+class Repo:
+    """rf_repo: a repository's object index in HBM -- batched Put / Stat /
+    Remove / Collect, and missing() / NeedTransfer for batches of values."""
+
+    def __init__(self, ctx: Context, capacity=0):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        _check(lib().rf_repo_new(ctx.handle, capacity, ctypes.byref(self._h)))
+
+    @staticmethod
+    def _ids(ids32):
+        ids = np.ascontiguousarray(ids32, dtype=np.uint8).reshape(-1)
+        assert len(ids) % 32 == 0
+        return ids, len(ids) // 32
+
+    def put(self, ids32, sizes) -> np.ndarray:
+        ids, n = self._ids(ids32)
+        sz = np.ascontiguousarray(sizes, dtype=np.int64)
+        assert len(sz) == n
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().rf_repo_put(self._h, _ptr(ids) if n else None, _ptr(sz) if n else None, n, _ptr(st)))
+        return st[:n]
+
+    def put_device(self, d_ids32, d_sizes, n, d_status, stream=None):
+        _check(lib().rf_repo_put_device(self._h, d_ids32, d_sizes, n, d_status, stream))
+
+    def remove(self, ids32) -> np.ndarray:
+        ids, n = self._ids(ids32)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(lib().rf_repo_remove(self._h, _ptr(ids) if n else None, n, _ptr(out)))
+        return out[:n]
+
+    def remove_device(self, d_ids32, n, d_removed, stream=None):
+        _check(lib().rf_repo_remove_device(self._h, d_ids32, n, d_removed, stream))
+
+    def stat(self, ids32) -> np.ndarray:
+        ids, n = self._ids(ids32)
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        _check(lib().rf_repo_stat(self._h, _ptr(ids) if n else None, n, _ptr(out)))
+        return out[:n]
+
+    def stat_device(self, d_ids32, n, d_sizes, stream=None):
+        _check(lib().rf_repo_stat_device(self._h, d_ids32, n, d_sizes, stream))
+
+    def collect(self, live=None, stream=None):
+        """Repository.Collect on the index: (objects removed, their bytes); live None removes everything."""
+        n, b = ctypes.c_uint64(), ctypes.c_int64()
+        _check(lib().rf_repo_collect(self._h, live._h if live is not None else None, ctypes.byref(n),
+                                     ctypes.byref(b), stream))
+        return n.value, b.value
+
+    def stats(self) -> RepoStats:
+        s = RepoStats()
+        _check(lib().rf_repo_stats_get(self._h, ctypes.byref(s), ctypes.sizeof(s)))
+        return s
+
+    def _host_out(self, n_groups, cap, want, poison):
+        """Host arrays for the fields in `want` (the others stay NULL), filled with the byte `poison`."""
+        res, o = RepoMissing(), RepoMissingOut()
+        shapes = {"n_files": (np.uint32, n_groups), "n_missing": (np.uint32, n_groups),
+                  "missing_bytes": (np.int64, n_groups), "status": (np.int32, n_groups),
+                  "miss_ptr": (np.uint64, n_groups + 1), "miss_rows": (np.uint64, cap),
+                  "miss_ids32": (np.uint8, 32 * cap), "miss_sizes": (np.int64, cap), "n_listed": (np.uint64, 1)}
+        for f in want:
+            dt, n = shapes[f]
+            a = np.frombuffer(bytes([poison]) * (max(n, 1) * np.dtype(dt).itemsize), dtype=dt).copy()
+            setattr(res, f, a)
+            setattr(o, f, a.ctypes.data)
+        o.cap = cap
+        return res, o
+
+    @staticmethod
+    def _trim(res, n_groups, cap, rc):
+        """Cut the arrays to their lengths; the list arrays keep all `cap` rows (the caller checks the cap rule)."""
+        for f, n in (("n_files", n_groups), ("n_missing", n_groups), ("missing_bytes", n_groups),
+                     ("status", n_groups), ("miss_ptr", n_groups + 1), ("miss_rows", cap), ("miss_sizes", cap)):
+            if getattr(res, f) is not None:
+                setattr(res, f, getattr(res, f)[:n])
+        if res.miss_ids32 is not None:
+            res.miss_ids32 = res.miss_ids32[:32 * cap].reshape(-1, 32)
+        if res.n_listed is not None:
+            res.n_listed = int(res.n_listed[0])
+        res.rc = rc
+        return res
+
+    def missing(self, counts, ids32, sizes, cap=None, want=RepoMissing.FIELDS, poison=0, check=True) -> RepoMissing:
+        """rf_repo_missing: counts[g] rows per group.  cap: rows of the list
+        arrays (default: every row could be listed).  check=False returns the
+        status in .rc instead of raising (the cap rule's RF_EINVAL)."""
+        ct = np.ascontiguousarray(counts, dtype=np.uint32)
+        ids, n = self._ids(ids32)
+        sz = np.ascontiguousarray(sizes, dtype=np.int64)
+        assert len(sz) == n
+        cap = n if cap is None else int(cap)
+        want = [f for f in want if f != "status"]
+        res, o = self._host_out(len(ct), cap, want, poison)
+        rc = lib().rf_repo_missing(self._h, _ptr(ct) if len(ct) else None, len(ct), _ptr(ids) if n else None,
+                                   _ptr(sz) if n else None, ctypes.byref(o))
+        if check:
+            _check(rc)
+        return self._trim(res, len(ct), cap, rc)
+
+    def missing_device(self, d_counts, n_groups, d_ids32, d_sizes, n_rows, out: RepoMissingOut, stream=None):
+        _check(lib().rf_repo_missing_device(self._h, d_counts, n_groups, d_ids32, d_sizes, n_rows, ctypes.byref(out),
+                                            stream))
+
+    def need_transfer(self, liveset, nodes, cap, want=RepoMissing.FIELDS, poison=0, check=True) -> RepoMissing:
+        """rf_repo_need_transfer: group g = the values of nodes[g]'s deps in `liveset` (a GcLiveset)."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        want = [f for f in want if f != "miss_rows"]
+        res, o = self._host_out(len(nd), int(cap), want, poison)
+        rc = lib().rf_repo_need_transfer(self._h, liveset._h, _ptr(nd) if len(nd) else None, len(nd), ctypes.byref(o))
+        if check:
+            _check(rc)
+        return self._trim(res, len(nd), int(cap), rc)
+
+    def need_transfer_device(self, liveset, d_nodes, n_nodes, out: RepoMissingOut, stream=None):
+        _check(lib().rf_repo_need_transfer_device(self._h, liveset._h, d_nodes, n_nodes, ctypes.byref(out), stream))
+
+    def close(self):
+        if self._h:
+            lib().rf_repo_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

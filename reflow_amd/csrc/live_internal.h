@@ -77,6 +77,12 @@ hipError_t launch_live_rows(const LiveDev& d, const LiveRows& r, const BloomDev&
 hipError_t launch_live_compare(const LiveDev& d, const uint64_t* a, const uint64_t* b, uint64_t nwords,
                                hipStream_t s);
 
+// liveset.cpp: the object behind rf_liveset*, as far as the repository index's
+// need_transfer (repo.cpp) needs it: its context, and the graph and value
+// records on the device (the view: context mutex held, and for as long as it is).
+rf_ctx* live_ctx(rf_liveset* l);
+const LiveDev& live_dev(rf_liveset* l);
+
 // capi.cpp: a filter the liveset owns and lends out (rf_bloom_destroy leaves
 // it alone).  *slot: null or a filter made here; it becomes an empty filter of
 // (m, k) with length m on s.  Context mutex held, device set.

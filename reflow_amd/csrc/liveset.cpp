@@ -47,6 +47,9 @@ struct rf_liveset {
     }
 };
 
+rf_ctx* rf::live_ctx(rf_liveset* l) { return l->ctx; }
+const LiveDev& rf::live_dev(rf_liveset* l) { return l->d; }
+
 static void live_free(rf_liveset* l) {
     for (DevBuf* b : l->all()) b->release();
     bloom_lent_free(l->filt[0]);

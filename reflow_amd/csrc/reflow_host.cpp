@@ -1470,4 +1470,120 @@ rf_liveset_stats GcLiveset::Stats() {
     return st;
 }
 
+// ---- repository index ----------------------------------------------------------------
+RepoIndex::RepoIndex(Engine& e, uint64_t capacity) { reflow::Check(rf_repo_new(e.ctx(), capacity, &r_)); }
+
+RepoIndex::~RepoIndex() { rf_repo_destroy(r_); }
+
+std::vector<int> RepoIndex::Put(const std::vector<Digest>& ids, const std::vector<int64_t>& sizes) {
+    if (ids.size() != sizes.size()) throw Error(RF_EINVAL, "RepoIndex: one size per ID");
+    std::vector<int32_t> st(ids.size() + 1);
+    reflow::Check(rf_repo_put(r_, ids.empty() ? nullptr : ids[0].b.data(), sizes.data(), ids.size(), st.data()));
+    return std::vector<int>(st.begin(), st.begin() + ids.size());
+}
+
+std::vector<int64_t> RepoIndex::Stat(const std::vector<Digest>& ids) {
+    std::vector<int64_t> out(ids.size() + 1);
+    reflow::Check(rf_repo_stat(r_, ids.empty() ? nullptr : ids[0].b.data(), ids.size(), out.data()));
+    out.resize(ids.size());
+    return out;
+}
+
+std::vector<bool> RepoIndex::Remove(const std::vector<Digest>& ids) {
+    std::vector<uint8_t> gone(ids.size() + 1);
+    reflow::Check(rf_repo_remove(r_, ids.empty() ? nullptr : ids[0].b.data(), ids.size(), gone.data()));
+    return std::vector<bool>(gone.begin(), gone.begin() + ids.size());
+}
+
+std::pair<uint64_t, int64_t> RepoIndex::Collect(const GcLiveset& live) {
+    if (!live.live_.b_) throw Error(RF_EPRECONDITION, "RepoIndex: the liveset has not been collected yet");
+    uint64_t n = 0;
+    int64_t bytes = 0;
+    reflow::Check(rf_repo_collect(r_, live.live_.b_, &n, &bytes, nullptr));
+    return {n, bytes};
+}
+
+std::pair<uint64_t, int64_t> RepoIndex::CollectAll() {
+    uint64_t n = 0;
+    int64_t bytes = 0;
+    reflow::Check(rf_repo_collect(r_, nullptr, &n, &bytes, nullptr));
+    return {n, bytes};
+}
+
+// One call with room for every row; the report cut to what was listed.
+template <class Call>
+static RepoIndex::Report repo_report(uint64_t groups, uint64_t cap, bool row_form, Call call) {
+    RepoIndex::Report rep;
+    rep.n_files.resize(groups + 1);
+    rep.n_missing.resize(groups + 1);
+    rep.missing_bytes.resize(groups + 1);
+    std::vector<int32_t> status(groups + 1);
+    rep.miss_ptr.resize(groups + 1);
+    rep.miss_rows.resize(cap + 1);
+    std::vector<Digest> ids(cap + 1);
+    std::vector<int64_t> sizes(cap + 1);
+    uint64_t listed = 0;
+    rf_repo_missing_out o{};
+    o.n_files = rep.n_files.data();
+    o.n_missing = rep.n_missing.data();
+    o.missing_bytes = rep.missing_bytes.data();
+    o.status = row_form ? nullptr : status.data();
+    o.cap = cap;
+    o.miss_ptr = rep.miss_ptr.data();
+    o.miss_rows = row_form ? rep.miss_rows.data() : nullptr;
+    o.miss_ids32 = ids[0].b.data();
+    o.miss_sizes = sizes.data();
+    o.n_listed = &listed;
+    reflow::Check(call(&o));
+    rep.n_files.resize(groups);
+    rep.n_missing.resize(groups);
+    rep.missing_bytes.resize(groups);
+    if (!row_form) rep.status.assign(status.begin(), status.begin() + groups);
+    rep.miss_rows.resize(row_form ? listed : 0);
+    rep.files.resize(listed);
+    for (uint64_t i = 0; i < listed; ++i) {
+        rep.files[i].ID = ids[i];
+        rep.files[i].Size = sizes[i];
+    }
+    return rep;
+}
+
+RepoIndex::Report RepoIndex::Missing(const std::vector<const Fileset*>& vals) {
+    std::vector<uint32_t> counts;
+    std::vector<Digest> ids;
+    std::vector<int64_t> sizes;
+    for (const Fileset* v : vals) {
+        const size_t before = ids.size();
+        flatten_rows(*v, ids, sizes);
+        counts.push_back((uint32_t)(ids.size() - before));
+    }
+    return repo_report(vals.size(), ids.size(), true, [&](rf_repo_missing_out* o) {
+        return rf_repo_missing(r_, counts.data(), counts.size(), ids.empty() ? nullptr : ids[0].b.data(), sizes.data(),
+                               o);
+    });
+}
+
+RepoIndex::Report RepoIndex::Missing(const std::vector<Fileset>& vals) {
+    std::vector<const Fileset*> p;
+    for (const Fileset& v : vals) p.push_back(&v);
+    return Missing(p);
+}
+
+RepoIndex::Report RepoIndex::NeedTransfer(GcLiveset& l, const std::vector<uint32_t>& nodes) {
+    // the list's size is not known before the call: count first (cap 0 with no list arrays), then list
+    uint64_t listed = 0;
+    rf_repo_missing_out count{};
+    count.n_listed = &listed;
+    reflow::Check(rf_repo_need_transfer(r_, l.l_, nodes.data(), nodes.size(), &count));
+    return repo_report(nodes.size(), listed, false, [&](rf_repo_missing_out* o) {
+        return rf_repo_need_transfer(r_, l.l_, nodes.data(), nodes.size(), o);
+    });
+}
+
+rf_repo_stats RepoIndex::Stats() {
+    rf_repo_stats st;
+    reflow::Check(rf_repo_stats_get(r_, &st, sizeof st));
+    return st;
+}
+
 }  // namespace reflow
