@@ -19,6 +19,7 @@ import pytest
 
 import reflow_oracle as O
 from flowgen import random_dag
+from hashkeys import keys_with_hash
 from lowering import Lowerer
 from reflow_oracle import OFlow
 
@@ -86,9 +87,8 @@ def test_dedup_random(ctx, n, classes):
 @pytest.mark.gpu
 def test_dedup_probe_collisions_and_hot_class(ctx):
     rng = np.random.default_rng(7)
-    # 4000 distinct digests sharing their first 8 bytes: one probe chain
-    d = rng.integers(0, 256, size=(4000, 32), dtype=np.uint8)
-    d[:, :8] = 0xAB
+    # 4000 distinct digests built to share their 32-bit key_hash: one probe chain
+    d = keys_with_hash(rng, 0xABABABAB, 4000)
     d = np.concatenate([d, d[::-1], d[::3]])  # each class several times
     canon, nu = ctx.dedup_digests(d)
     assert canon.tolist() == _first_occurrence(d).tolist() and nu == 4000
