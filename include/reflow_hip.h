@@ -635,9 +635,9 @@ int rf_flow_dirty(rf_ctx *ctx, uint64_t n, const uint64_t *dep_ptr, const uint32
  * node flagged DONE that is reached is DONE and is not expanded.  A node's
  * state depends on the node alone and the reached set is a closure, so every
  * result is independent of visit order and identical from run to run.
- * Out of scope: bottom-up mode (eval.go:940-941: its lookups wait for values
- * only the host has), dep.Err short-circuiting (eval.go:924-929), MapFlow,
- * Parent and continuations (Deps only, as Eval.todo), partitioned graphs.
+ * Out of scope: dep.Err short-circuiting (eval.go:924-929), MapFlow, Parent
+ * and continuations (Deps only, as Eval.todo), partitioned graphs.  Bottom-up
+ * mode and what follows the first round in either mode: rf_eval_wave below.
  * Device footprint of a plan (rf_eval_plan_stats' device_bytes): per node
  * 8 B dep pointer + 8 B key pointer + 4 B queue entry + 4 B hit-row index +
  * 4 B of flag / state / which / found bytes + bitmaps; 4 B per dep; 4 B per
@@ -729,6 +729,132 @@ int rf_eval_plan_list_device(rf_eval_plan *p, int state, uint64_t cap, void *d_n
                              void *d_vals32, void *d_key_found, void *d_found /* u64 */, void *stream);
 /* size = sizeof(rf_eval_plan_stats) of the caller's header. */
 int rf_eval_plan_stats_get(rf_eval_plan *p, rf_eval_plan_stats *out, uint64_t size);
+
+/* ---- Evaluation waves: bottom-up evaluation and the completion step
+ * (eval.go:902-955, 1163-1269, Deps only) ----
+ * Which nodes are ready now that these have finished.  The reference walks
+ * the graph from the roots on every scheduling step; an rf_eval_wave keeps,
+ * per node, PENDING -- the number of its dep entries whose dep has not
+ * finished -- and the consumer edges, so a step costs in proportion to what
+ * finished.  Node flags, states and key rows are the plan's (RF_PLAN_F_*,
+ * RF_PLAN_UNSEEN / TODO / READY / HIT / DONE, key_ptr / key_slots,
+ * RF_PLAN_MAX_KEYS); the object owns its own copy of the structure.
+ *   begin, bottom-up (-eval=bottomup, eval.go:301-321): from the listed roots
+ * every reached node not flagged DONE becomes TODO and all its deps are
+ * reached, with no lookups on the way down (eval.go:910); a reached node
+ * flagged DONE is DONE and is not expanded.  pending[i] = the dep entries of i
+ * whose dep is not flagged DONE; the reached nodes with none are wave 0.
+ *   begin from states, the top-down continuation: the state bytes of an
+ * rf_eval_plan (rejects applied).  TODO and READY nodes are tracked, HIT and
+ * DONE are satisfied (DONE here), UNSEEN stays; pending[i] = the dep entries
+ * whose dep is TODO or READY; wave 0 = the tracked nodes with none, i.e. the
+ * plan's READY list.  Nothing is ever looked up in this mode (eval.go:943-947).
+ *   A wave is resolved node by node.  Bottom-up, a node is looked up iff it is
+ * CACHEABLE, not INVALID, has at least one present key and, under
+ * no_cache_extern, is neither an EXTERN nor a listed root (eval.go:1173);
+ * rf_flow_dirty's closure is not consulted (Eval.lookup never calls dirty,
+ * only top-down todo does).  It is a HIT iff one of its present keys, not
+ * ruled out by the liveset, has a nonzero value in the assoc under `kind`
+ * (every present key is probed; which, the value -- copied out at lookup
+ * time -- and the found mask are kept); a miss is READY (lookupFailed in
+ * bottom-up mode is NeedTransfer, eval.go:1163-1166), and so is a node that
+ * is not looked up.  A key row of 32 zero bytes is absent (PhysicalDigest not
+ * computable yet, flow.go:762-774, 798-800): not probed, not counted, its
+ * found bit clear; `which` stays the row index.
+ *   step: the listed nodes have finished -- they ran, or they are hits the
+ * caller accepted (unmarshal, rf_repo_missing).  Each must be READY or HIT
+ * (RF_EINVAL otherwise, the object untouched); a node listed twice counts
+ * once.  They become DONE, every consumer entry of each whose consumer is
+ * tracked takes one decrement of pending, and the consumers that reach zero
+ * are the next wave, resolved as above with the keys as they are now (a
+ * consumer's physical key moves when its deps' values are set).  There is no
+ * cascade inside a step: a hit is not DONE until the caller says so.
+ *   reject: the listed HITs failed the caller's post-checks and become READY.
+ * Every result depends only on the set of nodes finished so far, and the
+ * decrement that reaches zero is unique, so states, lists and counts are
+ * identical from run to run.  Calls hold the context's lock and return when
+ * complete; every object of one context (RF_EINVAL).
+ * Out of scope: dep.Err short-circuiting (eval.go:924-929); MapFlow, Parent
+ * and continuations, graphs that grow at run time; partitioned graphs; any
+ * hand-off between workgroups inside a kernel -- everything one kernel writes
+ * for the next is read only after the kernel boundary.
+ * Device footprint (rf_eval_wave_stats' device_bytes): per node 8 B dep
+ * pointer + 8 B consumer pointer + 8 B key pointer + 4 B pending + 4 B + 4 B
+ * queue entries + 4 B hit-row index + 4 B of flag / state / which / found
+ * bytes + four bitmaps; 8 B per dep entry (dep and consumer); 4 B per key
+ * slot; 32 B per node that has keys; plus, for the host-form calls, 32 B per
+ * key row, 1 B per node of begin_states input and the list staging. */
+typedef struct rf_eval_wave rf_eval_wave;
+/* list scopes */
+#define RF_WAVE_ALL 0  /* every node in the state */
+#define RF_WAVE_LAST 1 /* only nodes that entered by the last begin or step */
+typedef struct {
+    uint64_t n_nodes;
+    uint64_t n_deps;      /* dep entries = consumer entries */
+    uint32_t depth;       /* nodes on the longest path: the bound on descent rounds */
+    uint32_t mode;        /* 0: no begin yet, 1: bottom-up, 2: top-down continuation */
+    uint32_t waves;       /* begin and step calls since (and with) the last begin */
+    uint32_t last_wave;   /* nodes that entered by the last begin or step */
+    uint32_t rounds;      /* descent launches of the last begin */
+    uint32_t round_batch; /* descent rounds enqueued between two host reads */
+    uint32_t wave_lanes;  /* lanes of one descent / resolve launch (a fixed grid that strides) */
+    uint32_t list_tile;   /* nodes per tile of the list's mark / scan / scatter */
+    uint64_t counts[5];   /* nodes per state now */
+    uint64_t looked_up;   /* nodes looked up by the last begin or step */
+    uint64_t keys_probed; /* their keys that went to the assoc */
+    uint64_t keys_filtered; /* their keys the liveset ruled out */
+    uint64_t device_bytes;
+} rf_eval_wave_stats;
+/* Host only, no context: the consumer CSR of rf_eval_plan_open's dep CSR.
+ * cons_ptr [n+1], cons [dep_ptr[n]]: for node d the nodes that list d as a
+ * dep, one entry per dep entry (a dep listed twice gives two), ascending
+ * within a node.  RF_EINVAL as rf_eval_plan_check (a cycle included) and for
+ * a NULL output. */
+int rf_eval_wave_consumers(uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, uint64_t *cons_ptr,
+                           uint32_t *cons);
+/* rf_eval_plan_open's arguments and checks. */
+int rf_eval_wave_open(rf_ctx *ctx, uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, const uint8_t *flags,
+                      const uint64_t *key_ptr, const uint32_t *key_slots, rf_eval_wave **out);
+void rf_eval_wave_close(rf_eval_wave *w);
+/* Replace the flag bytes of the listed nodes, for the next begin. */
+int rf_eval_wave_set_flags(rf_eval_wave *w, const uint32_t *nodes, const uint8_t *flags, uint64_t n);
+/* Begin bottom-up from `roots` (host array; duplicates are harmless) and
+ * resolve wave 0.  Keys, live, a, kind, stream: as rf_eval_plan_run. */
+int rf_eval_wave_begin(rf_eval_wave *w, const uint32_t *roots, uint64_t n_roots, int no_cache_extern, rf_graph *g,
+                       const void *d_keys32, rf_bloom *live, rf_assoc *a, int kind, void *stream);
+int rf_eval_wave_begin_host(rf_eval_wave *w, const uint32_t *roots, uint64_t n_roots, int no_cache_extern,
+                            const uint8_t *keys32, rf_bloom *live, rf_assoc *a, int kind);
+/* Begin from one RF_PLAN_* byte per node (rf_eval_plan_states, or with
+ * on_device rf_eval_plan_states_device; the bytes are copied).  RF_EINVAL,
+ * the object unchanged, for a byte above RF_PLAN_DONE or a TODO / READY node
+ * with an UNSEEN dep. */
+int rf_eval_wave_begin_states(rf_eval_wave *w, const void *state, int on_device, void *stream);
+/* The listed nodes (host array) have finished; the next wave is resolved.
+ * n == 0 is valid and gives an empty wave.  Keys as rf_eval_wave_begin, read
+ * now: with g, RF_EPRECONDITION while an input change is pending.  In the
+ * top-down continuation keys, live and a are not read and may be NULL.
+ * RF_EPRECONDITION before any begin. */
+int rf_eval_wave_step(rf_eval_wave *w, const uint32_t *nodes, uint64_t n, rf_graph *g, const void *d_keys32,
+                      rf_bloom *live, rf_assoc *a, int kind, void *stream);
+int rf_eval_wave_step_host(rf_eval_wave *w, const uint32_t *nodes, uint64_t n, const uint8_t *keys32, rf_bloom *live,
+                           rf_assoc *a, int kind);
+/* These hits failed the caller's post-checks: READY.  RF_EINVAL, the object
+ * untouched, if one of them is not a HIT. */
+int rf_eval_wave_reject(rf_eval_wave *w, const uint32_t *nodes, uint64_t n);
+/* One RF_PLAN_* byte per node, as of now. */
+int rf_eval_wave_states(rf_eval_wave *w, uint8_t *state);
+int rf_eval_wave_states_device(rf_eval_wave *w, const void **d_state);
+/* rf_eval_plan_list's rules (strictly ascending, a tile mark / scan / scatter
+ * over the state array; which / vals32 / key_found for RF_PLAN_HIT; the cap
+ * rule), over every node (RF_WAVE_ALL) or only the members of the last wave
+ * (RF_WAVE_LAST: a bitmap cleared per step carries the membership; a member
+ * that a reject made READY is still a member). */
+int rf_eval_wave_list(rf_eval_wave *w, int state, int scope, uint64_t cap, uint32_t *nodes, uint8_t *which,
+                      uint8_t *vals32, uint8_t *key_found, uint64_t *found);
+int rf_eval_wave_list_device(rf_eval_wave *w, int state, int scope, uint64_t cap, void *d_nodes, void *d_which,
+                             void *d_vals32, void *d_key_found, void *d_found /* u64 */, void *stream);
+/* size = sizeof(rf_eval_wave_stats) of the caller's header. */
+int rf_eval_wave_stats_get(rf_eval_wave *w, rf_eval_wave_stats *out, uint64_t size);
 
 /* ---- GC liveset: Eval.collect's walk, dedup and filter build (eval.go:791-868) ----
  * What is live, as a bloom filter, without a host walk of the graph.  An

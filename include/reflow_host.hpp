@@ -497,6 +497,7 @@ class Eval {
    private:
     friend Flow* Canonicalize(Engine&, FlowArena&, Flow*, Config, const std::string&, std::unique_ptr<Eval>*);
     friend class EvalPlan;  // (Run / Reject with keys from the graph)
+    friend class EvalWave;  // (Begin / Step with keys from the graph)
     using Holes = std::vector<std::pair<uint32_t, uint32_t>>;  // (byte pos, slot)
     // File IDs referenced from a job's material (file slots): (its hole's
     // index in the job, the ID) -- slots are given after the parallel phase
@@ -572,6 +573,7 @@ class Liveset {
    private:
     friend class Eval;      // (FeedLookup)
     friend class EvalPlan;  // (Run / Reject)
+    friend class EvalWave;  // (Begin / Step)
     friend class GcLiveset; // (Collect lends its filter)
     friend class RepoIndex; // (Collect reads it)
     explicit Liveset(rf_bloom* b) : b_(b) {}
@@ -627,6 +629,7 @@ class Assoc {
    private:
     friend class Eval;      // (FeedLookup)
     friend class EvalPlan;  // (Run / Reject)
+    friend class EvalWave;  // (Begin / Step)
     Assoc() = default;
     rf_assoc* a_ = nullptr;
 };
@@ -675,7 +678,51 @@ class EvalPlan {
     rf_eval_plan_stats Stats();
 
    private:
+    friend class EvalWave;  // (BeginStates reads the plan's states on the device)
     rf_eval_plan* p_ = nullptr;
+    uint64_t n_keys_ = 0;
+};
+
+// Bottom-up evaluation and the completion step of either mode, on the device
+// (rf_eval_wave_*; eval.go:902-955, 1163-1269, Deps only): which nodes are
+// ready now that these have finished.  The constructor takes EvalPlan's
+// arguments.  Bottom-up: Begin, then per scheduling step Reject the hits that
+// fail the caller's checks, run what is READY, set the finished nodes' values
+// and Step.  Top-down: EvalPlan::Run, BeginStates(plan), then Step.
+class EvalWave {
+   public:
+    EvalWave(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+             const std::vector<uint8_t>& flags, const std::vector<uint64_t>& key_ptr,
+             const std::vector<uint32_t>* key_slots = nullptr);
+    ~EvalWave();
+    EvalWave(const EvalWave&) = delete;
+    EvalWave& operator=(const EvalWave&) = delete;
+    // The consumer CSR on the host alone: (cons_ptr, cons); throws
+    // Error(RF_EINVAL) for a cycle or a malformed CSR.
+    static std::pair<std::vector<uint64_t>, std::vector<uint32_t>> Consumers(const std::vector<uint64_t>& dep_ptr,
+                                                                             const std::vector<uint32_t>& deps);
+    void SetFlags(const std::vector<uint32_t>& nodes, const std::vector<uint8_t>& flags);  // for the next Begin
+    // keys: one row per key_ptr row (a row of zeros: absent); live may be null.
+    void Begin(const std::vector<uint32_t>& roots, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+               AssocKind kind, bool no_cache_extern = false);
+    void Begin(const std::vector<uint32_t>& roots, Eval& ev, Liveset* live, Assoc& a, AssocKind kind,
+               bool no_cache_extern = false);
+    void BeginStates(const std::vector<uint8_t>& states);  // one RF_PLAN_* per node
+    void BeginStates(EvalPlan& plan);                      // the plan's states, read on the device
+    // The listed nodes have finished; the next wave is resolved with the keys as they are now.
+    void Step(const std::vector<uint32_t>& finished, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+              AssocKind kind);
+    void Step(const std::vector<uint32_t>& finished, Eval& ev, Liveset* live, Assoc& a, AssocKind kind);
+    void Step(const std::vector<uint32_t>& finished);  // the top-down continuation: nothing is looked up
+    void Reject(const std::vector<uint32_t>& nodes);   // these hits failed the caller's checks: READY
+    std::vector<uint8_t> States();
+    std::vector<uint32_t> List(int state, int scope = RF_WAVE_ALL);  // ascending node ids
+    using Hit = EvalPlan::Hit;
+    std::vector<Hit> Hits(int scope = RF_WAVE_ALL);
+    rf_eval_wave_stats Stats();
+
+   private:
+    rf_eval_wave* w_ = nullptr;
     uint64_t n_keys_ = 0;
 };
 

@@ -33,6 +33,9 @@ FEED_TILE_SLOTS = 8192
 RF_PLAN_F_CACHEABLE, RF_PLAN_F_EXTERN, RF_PLAN_F_INVALID, RF_PLAN_F_DONE = 1, 2, 4, 8
 RF_PLAN_UNSEEN, RF_PLAN_TODO, RF_PLAN_READY, RF_PLAN_HIT, RF_PLAN_DONE = range(5)
 RF_PLAN_MAX_KEYS = 8
+# evaluation waves (rf_eval_wave_*): list scopes, modes
+RF_WAVE_ALL, RF_WAVE_LAST = 0, 1
+RF_WAVE_MODE_NONE, RF_WAVE_MODE_BOTTOMUP, RF_WAVE_MODE_TOPDOWN = 0, 1, 2
 # GC liveset (rf_liveset_*): node states, rows per run, nodes per list tile, rounds per host read
 RF_LIVE_UNSEEN, RF_LIVE_WALKED, RF_LIVE_VALUE = range(3)
 RF_LIVE_MAX_ROWS = 1 << 30
@@ -82,6 +85,10 @@ EXPORTS = [
     "rf_eval_plan_run", "rf_eval_plan_run_host", "rf_eval_plan_reject", "rf_eval_plan_reject_host",
     "rf_eval_plan_states", "rf_eval_plan_states_device", "rf_eval_plan_list", "rf_eval_plan_list_device",
     "rf_eval_plan_stats_get",
+    "rf_eval_wave_consumers", "rf_eval_wave_open", "rf_eval_wave_close", "rf_eval_wave_set_flags",
+    "rf_eval_wave_begin", "rf_eval_wave_begin_host", "rf_eval_wave_begin_states", "rf_eval_wave_step",
+    "rf_eval_wave_step_host", "rf_eval_wave_reject", "rf_eval_wave_states", "rf_eval_wave_states_device",
+    "rf_eval_wave_list", "rf_eval_wave_list_device", "rf_eval_wave_stats_get",
     "rf_bloom_estimate", "rf_liveset_open", "rf_liveset_close", "rf_liveset_set_values",
     "rf_liveset_set_values_device", "rf_liveset_clear_values", "rf_liveset_run", "rf_liveset_filter",
     "rf_liveset_states", "rf_liveset_list", "rf_liveset_stats_get",
@@ -293,6 +300,17 @@ class EvalPlanStats(ctypes.Structure):
                 ("device_bytes", ctypes.c_uint64)]
 
 
+class EvalWaveStats(ctypes.Structure):
+    """rf_eval_wave_stats: counts[state] as of now; the lookup figures are those of the last begin / step."""
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_deps", ctypes.c_uint64), ("depth", ctypes.c_uint32),
+                ("mode", ctypes.c_uint32), ("waves", ctypes.c_uint32), ("last_wave", ctypes.c_uint32),
+                ("rounds", ctypes.c_uint32), ("round_batch", ctypes.c_uint32),
+                ("wave_lanes", ctypes.c_uint32), ("list_tile", ctypes.c_uint32),
+                ("counts", ctypes.c_uint64 * 5), ("looked_up", ctypes.c_uint64),
+                ("keys_probed", ctypes.c_uint64), ("keys_filtered", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64)]
+
+
 class LivesetStats(ctypes.Structure):
     """rf_liveset_stats: the figures of the last run (arena_rows / stale_rows: as of now)."""
     _fields_ = [("n_nodes", ctypes.c_uint64), ("counts", ctypes.c_uint64 * 3), ("contributions", ctypes.c_uint64),
@@ -474,6 +492,19 @@ def lib():
             "rf_eval_plan_list": ([vp, i32, u64, vp, vp, vp, vp, vp], i32),
             "rf_eval_plan_list_device": ([vp, i32, u64, vp, vp, vp, vp, vp, vp], i32),
             "rf_eval_plan_stats_get": ([vp, vp, u64], i32),
+            "rf_eval_wave_consumers": ([u64, vp, vp, vp, vp], i32),
+            "rf_eval_wave_open": ([vp, u64, vp, vp, vp, vp, vp, vp], i32), "rf_eval_wave_close": ([vp], None),
+            "rf_eval_wave_set_flags": ([vp, vp, vp, u64], i32),
+            "rf_eval_wave_begin": ([vp, vp, u64, i32, vp, vp, vp, vp, i32, vp], i32),
+            "rf_eval_wave_begin_host": ([vp, vp, u64, i32, vp, vp, vp, i32], i32),
+            "rf_eval_wave_begin_states": ([vp, vp, i32, vp], i32),
+            "rf_eval_wave_step": ([vp, vp, u64, vp, vp, vp, vp, i32, vp], i32),
+            "rf_eval_wave_step_host": ([vp, vp, u64, vp, vp, vp, i32], i32),
+            "rf_eval_wave_reject": ([vp, vp, u64], i32),
+            "rf_eval_wave_states": ([vp, vp], i32), "rf_eval_wave_states_device": ([vp, vp], i32),
+            "rf_eval_wave_list": ([vp, i32, i32, u64, vp, vp, vp, vp, vp], i32),
+            "rf_eval_wave_list_device": ([vp, i32, i32, u64, vp, vp, vp, vp, vp, vp], i32),
+            "rf_eval_wave_stats_get": ([vp, vp, u64], i32),
             "rf_bloom_estimate": ([u64, ctypes.c_double, vp, vp], i32),
             "rf_liveset_open": ([vp, u64, vp, vp, vp], i32), "rf_liveset_close": ([vp], None),
             "rf_liveset_set_values": ([vp, vp, vp, u64, vp, vp], i32),
@@ -1513,6 +1544,154 @@ class EvalPlan:
     def close(self):
         if self._h:
             lib().rf_eval_plan_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def eval_wave_consumers(dep_ptr, deps):
+    """rf_eval_wave_consumers (host only): (cons_ptr uint64 [n+1], cons uint32):
+    for node d the nodes that list d as a dep, one entry per dep entry,
+    ascending within a node; RfError RF_EINVAL as eval_plan_check."""
+    dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+    de = np.ascontiguousarray(deps, dtype=np.uint32)
+    n = max(len(dp) - 1, 0)
+    cp = np.zeros(n + 1, dtype=np.uint64)
+    co = np.zeros(max(len(de), 1), dtype=np.uint32)
+    _check(lib().rf_eval_wave_consumers(n, _ptr(dp) if len(dp) else None, _ptr(de) if len(de) else None,
+                                        _ptr(cp), _ptr(co)))
+    return cp, co[:len(de)]
+
+
+class EvalWave:
+    """rf_eval_wave: bottom-up evaluation and the completion step on the
+    device.  The constructor takes EvalPlan's arguments.  begin() starts
+    bottom-up from roots, begin_states() continues a top-down plan; step()
+    takes the nodes that finished and resolves the nodes that became ready;
+    reject() turns hits the caller's checks refused into READY."""
+
+    def __init__(self, ctx: Context, dep_ptr, deps, flags, key_ptr, key_slots=None):
+        self.ctx = ctx
+        dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+        de = np.ascontiguousarray(deps, dtype=np.uint32)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        kp = np.ascontiguousarray(key_ptr, dtype=np.uint64)
+        ks = None if key_slots is None else np.ascontiguousarray(key_slots, dtype=np.uint32)
+        self.n = len(fl)
+        self.n_keys = int(kp[-1]) if len(kp) else 0
+        self._h = ctypes.c_void_p()
+        _check(lib().rf_eval_wave_open(ctx.handle, self.n, _ptr(dp) if self.n else None,
+                                       _ptr(de) if len(de) else None, _ptr(fl) if self.n else None,
+                                       _ptr(kp) if self.n else None,
+                                       None if ks is None else (_ptr(ks) if len(ks) else _ptr(np.zeros(1, np.uint32))),
+                                       ctypes.byref(self._h)))
+
+    def set_flags(self, nodes, flags):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert len(nd) == len(fl)
+        _check(lib().rf_eval_wave_set_flags(self._h, _ptr(nd) if len(nd) else None, _ptr(fl) if len(fl) else None,
+                                            len(nd)))
+
+    @staticmethod
+    def _h_of(o):
+        return None if o is None else o._h
+
+    def _host_keys(self, keys):
+        k = np.ascontiguousarray(keys if keys is not None else np.zeros(0, np.uint8), dtype=np.uint8).reshape(-1)
+        assert len(k) == 32 * self.n_keys
+        return k
+
+    def begin(self, roots, assoc, kind, keys=None, graph=None, d_keys=None, live=None, no_cache_extern=False,
+              stream=None):
+        """Bottom-up from `roots`; wave 0 is resolved.  Keys as EvalPlan.run."""
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        rp = _ptr(r) if len(r) else None
+        if graph is None and d_keys is None:
+            k = self._host_keys(keys)
+            _check(lib().rf_eval_wave_begin_host(self._h, rp, len(r), int(bool(no_cache_extern)),
+                                                 _ptr(k) if len(k) else None, self._h_of(live), assoc._h, kind))
+        else:
+            _check(lib().rf_eval_wave_begin(self._h, rp, len(r), int(bool(no_cache_extern)), self._h_of(graph),
+                                            d_keys, self._h_of(live), assoc._h, kind, stream))
+
+    def begin_states(self, states=None, d_states=None, stream=None):
+        """The top-down continuation: states (host bytes, one per node) or
+        d_states (a device pointer, EvalPlan.states_device())."""
+        if d_states is not None:
+            _check(lib().rf_eval_wave_begin_states(self._h, d_states, 1, stream))
+        else:
+            st = np.ascontiguousarray(states, dtype=np.uint8)
+            assert len(st) == self.n
+            _check(lib().rf_eval_wave_begin_states(self._h, _ptr(st) if self.n else None, 0, stream))
+
+    def step(self, nodes, assoc=None, kind=0, keys=None, graph=None, d_keys=None, live=None, stream=None):
+        """The listed nodes have finished; the next wave is resolved."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        np_ = _ptr(nd) if len(nd) else None
+        if graph is None and d_keys is None:
+            k = None if keys is None else self._host_keys(keys)
+            _check(lib().rf_eval_wave_step_host(self._h, np_, len(nd), _ptr(k) if k is not None and len(k) else None,
+                                                self._h_of(live), self._h_of(assoc), kind))
+        else:
+            _check(lib().rf_eval_wave_step(self._h, np_, len(nd), self._h_of(graph), d_keys, self._h_of(live),
+                                           self._h_of(assoc), kind, stream))
+
+    def reject(self, nodes):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        _check(lib().rf_eval_wave_reject(self._h, _ptr(nd) if len(nd) else None, len(nd)))
+
+    def states(self) -> np.ndarray:
+        out = np.zeros(max(self.n, 1), dtype=np.uint8)
+        _check(lib().rf_eval_wave_states(self._h, _ptr(out)))
+        return out[:self.n]
+
+    def states_device(self) -> int:
+        p = ctypes.c_void_p()
+        _check(lib().rf_eval_wave_states_device(self._h, ctypes.byref(p)))
+        return p.value
+
+    def count(self, state, scope=RF_WAVE_ALL) -> int:
+        n = ctypes.c_uint64()
+        rc = lib().rf_eval_wave_list(self._h, state, scope, 0, None, None, None, None, ctypes.byref(n))
+        if rc != RF_OK and not (rc == RF_EINVAL and n.value):
+            _check(rc)
+        return n.value
+
+    def list(self, state, scope=RF_WAVE_ALL, cap=None, poison=None):
+        """rf_eval_wave_list: as EvalPlan.list, over every node or the last wave."""
+        cap = self.count(state, scope) if cap is None else int(cap)
+        fill = 0 if poison is None else poison
+        nodes = np.full(max(cap, 1), fill * 0x01010101, dtype=np.uint32)
+        which = np.full(max(cap, 1), fill, dtype=np.uint8)
+        vals = np.full((max(cap, 1), 32), fill, dtype=np.uint8)
+        kf = np.full(max(cap, 1), fill, dtype=np.uint8)
+        n = ctypes.c_uint64()
+        rc = lib().rf_eval_wave_list(self._h, state, scope, cap, _ptr(nodes), _ptr(which), _ptr(vals), _ptr(kf),
+                                     ctypes.byref(n))
+        if rc != RF_OK:
+            err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+            err.needed = n.value
+            err.buffers = (nodes, which, vals, kf)
+            raise err
+        return nodes[:n.value], which[:n.value], vals[:n.value], kf[:n.value]
+
+    def list_device(self, state, scope, cap, d_nodes, d_which, d_vals, d_key_found, d_found, stream=None):
+        _check(lib().rf_eval_wave_list_device(self._h, state, scope, cap, d_nodes, d_which, d_vals, d_key_found,
+                                              d_found, stream))
+
+    def stats(self) -> EvalWaveStats:
+        s = EvalWaveStats()
+        _check(lib().rf_eval_wave_stats_get(self._h, ctypes.byref(s), ctypes.sizeof(s)))
+        return s
+
+    def close(self):
+        if self._h:
+            lib().rf_eval_wave_close(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

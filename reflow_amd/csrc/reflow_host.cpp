@@ -1402,6 +1402,119 @@ rf_eval_plan_stats EvalPlan::Stats() {
     return st;
 }
 
+// ---- evaluation waves -----------------------------------------------------------
+EvalWave::EvalWave(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+                   const std::vector<uint8_t>& flags, const std::vector<uint64_t>& key_ptr,
+                   const std::vector<uint32_t>* key_slots) {
+    const uint64_t n = flags.size();
+    if (dep_ptr.size() != n + 1 || key_ptr.size() != n + 1) throw Error(RF_EINVAL, "EvalWave: pointer arrays need n + 1 entries");
+    n_keys_ = key_ptr.back();
+    if (dep_ptr.back() != deps.size() || (key_slots && key_slots->size() != n_keys_))
+        throw Error(RF_EINVAL, "EvalWave: array lengths do not match the pointers");
+    static const uint32_t none = 0;
+    reflow::Check(rf_eval_wave_open(e.ctx(), n, dep_ptr.data(), deps.data(), flags.data(), key_ptr.data(),
+                                    key_slots ? (key_slots->empty() ? &none : key_slots->data()) : nullptr, &w_));
+}
+
+EvalWave::~EvalWave() { rf_eval_wave_close(w_); }
+
+std::pair<std::vector<uint64_t>, std::vector<uint32_t>> EvalWave::Consumers(const std::vector<uint64_t>& dep_ptr,
+                                                                            const std::vector<uint32_t>& deps) {
+    const uint64_t n = dep_ptr.empty() ? 0 : dep_ptr.size() - 1;
+    std::vector<uint64_t> cons_ptr(n + 1);
+    std::vector<uint32_t> cons(deps.size() + 1);
+    reflow::Check(rf_eval_wave_consumers(n, dep_ptr.data(), deps.data(), cons_ptr.data(), cons.data()));
+    cons.resize(deps.size());
+    return {std::move(cons_ptr), std::move(cons)};
+}
+
+void EvalWave::SetFlags(const std::vector<uint32_t>& nodes, const std::vector<uint8_t>& flags) {
+    if (nodes.size() != flags.size()) throw Error(RF_EINVAL, "SetFlags: one flag byte per node");
+    reflow::Check(rf_eval_wave_set_flags(w_, nodes.data(), flags.data(), nodes.size()));
+}
+
+void EvalWave::Begin(const std::vector<uint32_t>& roots, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+                     AssocKind kind, bool no_cache_extern) {
+    if (keys.size() != n_keys_) throw Error(RF_EINVAL, "EvalWave: one key per key row");
+    reflow::Check(rf_eval_wave_begin_host(w_, roots.data(), roots.size(), no_cache_extern,
+                                          keys.empty() ? nullptr : keys[0].b.data(), live ? live->b_ : nullptr, a.a_,
+                                          kind));
+}
+
+void EvalWave::Begin(const std::vector<uint32_t>& roots, Eval& ev, Liveset* live, Assoc& a, AssocKind kind,
+                     bool no_cache_extern) {
+    reflow::Check(rf_eval_wave_begin(w_, roots.data(), roots.size(), no_cache_extern, ev.g_, nullptr,
+                                     live ? live->b_ : nullptr, a.a_, kind, nullptr));
+}
+
+void EvalWave::BeginStates(const std::vector<uint8_t>& states) {
+    if (states.size() != Stats().n_nodes) throw Error(RF_EINVAL, "EvalWave: one state byte per node");
+    reflow::Check(rf_eval_wave_begin_states(w_, states.data(), 0, nullptr));
+}
+
+void EvalWave::BeginStates(EvalPlan& plan) {
+    if (plan.Stats().n_nodes != Stats().n_nodes) throw Error(RF_EINVAL, "EvalWave: the plan is of another graph");
+    const void* d_state = nullptr;
+    reflow::Check(rf_eval_plan_states_device(plan.p_, &d_state));
+    reflow::Check(rf_eval_wave_begin_states(w_, d_state, 1, nullptr));
+}
+
+void EvalWave::Step(const std::vector<uint32_t>& finished, const std::vector<Digest>& keys, Liveset* live, Assoc& a,
+                    AssocKind kind) {
+    if (keys.size() != n_keys_) throw Error(RF_EINVAL, "EvalWave: one key per key row");
+    reflow::Check(rf_eval_wave_step_host(w_, finished.data(), finished.size(), keys.empty() ? nullptr : keys[0].b.data(),
+                                         live ? live->b_ : nullptr, a.a_, kind));
+}
+
+void EvalWave::Step(const std::vector<uint32_t>& finished, Eval& ev, Liveset* live, Assoc& a, AssocKind kind) {
+    reflow::Check(rf_eval_wave_step(w_, finished.data(), finished.size(), ev.g_, nullptr, live ? live->b_ : nullptr,
+                                    a.a_, kind, nullptr));
+}
+
+void EvalWave::Step(const std::vector<uint32_t>& finished) {
+    if (Stats().mode == 1) throw Error(RF_EINVAL, "EvalWave: a bottom-up step needs keys and an assoc");
+    reflow::Check(rf_eval_wave_step_host(w_, finished.data(), finished.size(), nullptr, nullptr, nullptr, 0));
+}
+
+void EvalWave::Reject(const std::vector<uint32_t>& nodes) {
+    reflow::Check(rf_eval_wave_reject(w_, nodes.data(), nodes.size()));
+}
+
+std::vector<uint8_t> EvalWave::States() {
+    std::vector<uint8_t> st(Stats().n_nodes);
+    reflow::Check(rf_eval_wave_states(w_, st.data()));
+    return st;
+}
+
+std::vector<uint32_t> EvalWave::List(int state, int scope) {
+    if (state < RF_PLAN_UNSEEN || state > RF_PLAN_DONE) throw Error(RF_EINVAL, "EvalWave: unknown state");
+    const rf_eval_wave_stats st = Stats();
+    std::vector<uint32_t> nodes(scope == RF_WAVE_LAST ? std::min<uint64_t>(st.last_wave, st.counts[state]) : st.counts[state]);
+    uint64_t found = 0;
+    reflow::Check(rf_eval_wave_list(w_, state, scope, nodes.size(), nodes.data(), nullptr, nullptr, nullptr, &found));
+    nodes.resize(found);
+    return nodes;
+}
+
+std::vector<EvalWave::Hit> EvalWave::Hits(int scope) {
+    const uint64_t cap = Stats().counts[RF_PLAN_HIT];
+    std::vector<uint32_t> nodes(cap);
+    std::vector<uint8_t> which(cap), kf(cap);
+    std::vector<Digest> vals(cap);
+    uint64_t found = 0;
+    reflow::Check(rf_eval_wave_list(w_, RF_PLAN_HIT, scope, cap, nodes.data(), which.data(),
+                                    cap ? vals[0].b.data() : nullptr, kf.data(), &found));
+    std::vector<Hit> out(found);
+    for (uint64_t i = 0; i < found; ++i) out[i] = Hit{nodes[i], which[i], vals[i], kf[i]};
+    return out;
+}
+
+rf_eval_wave_stats EvalWave::Stats() {
+    rf_eval_wave_stats st{};
+    reflow::Check(rf_eval_wave_stats_get(w_, &st, sizeof st));
+    return st;
+}
+
 // ---- GC liveset -------------------------------------------------------------------
 GcLiveset::GcLiveset(Engine& e, const std::vector<uint64_t>& edge_ptr, const std::vector<uint32_t>& edges) {
     if (edge_ptr.empty() || edge_ptr.back() != edges.size())
