@@ -186,12 +186,20 @@ void rf_sha_plan_destroy(rf_sha_plan *plan);
  * split is priced with (default 1.0); RF_SHA_PREFIX_CKPT, the blocks between
  * two chaining values (a multiple of 64, default 2048); and, for tests,
  * RF_SHA_PREFIX_PRECLAIM=1: every message counts as claimed before the
- * launch, so each wave stops at its first value. */
+ * launch, so each wave stops at its first value.
+ *
+ * Lone lanes.  The first n_lone host-leg messages (the largest) each run alone
+ * on their host thread: its other lanes take nothing until that message ends,
+ * so the chains that would set the step run at the one-lane rate.  Chosen by
+ * the planner's schedule model for the plans that get prefixes; never for
+ * all-host, host-resident or one-lane-chain plans.  RF_SHA_LONE=<k> in the
+ * environment when the plan is created forces k (0: none). */
 typedef struct {
     uint64_t n_prefixed;    /* host-leg messages with a prefix                 */
     uint64_t planned_bytes; /* 64 x the most blocks their waves may hash       */
     uint64_t taken, missed; /* last run: prefixes found ready / not ready      */
     uint64_t skipped_bytes; /* last run: bytes the host leg did not hash       */
+    uint64_t n_lone;        /* host-leg messages that run alone on their thread */
 } rf_sha_prefix_stats;
 int rf_sha_plan_prefix_stats(rf_sha_plan *plan, rf_sha_prefix_stats *out);
 /* Test control.  prefix_blocks[i] (NULL: keep the plan's) replaces the prefix

@@ -107,7 +107,7 @@ class RfError(RuntimeError):
 class ShaPrefixStats(ctypes.Structure):
     """rf_sha_prefix_stats: the plan's prefix hand-overs and what the last run's host leg made of them."""
     _fields_ = [("n_prefixed", ctypes.c_uint64), ("planned_bytes", ctypes.c_uint64), ("taken", ctypes.c_uint64),
-                ("missed", ctypes.c_uint64), ("skipped_bytes", ctypes.c_uint64)]
+                ("missed", ctypes.c_uint64), ("skipped_bytes", ctypes.c_uint64), ("n_lone", ctypes.c_uint64)]
 
 
 class ShaStats(ctypes.Structure):

@@ -328,6 +328,7 @@ struct rf_sha_plan {
     bool side_ran = false;      // the last run launched on the side stream
     bool side_pending = false;  // ... and e_solo has not been waited for since
     HostLegStats pfx_last{};
+    uint32_t n_lone = 0;  // the first n_lone host tasks run alone on their thread
 };
 
 // Measured per-block chain latencies of the GPU legs:
@@ -423,6 +424,38 @@ static constexpr double kPrefixAlpha = 1.0;
 static constexpr double kPrefixCapAlpha = 1.25;
 static constexpr uint64_t kPrefixCkptBlocks = 2048;
 
+// Lone lanes (host_sched.h, DESIGN.md §5 "Lone lanes"): how many of the first
+// messages run alone on their threads, lone in [lo, hi], and the leg's
+// modelled makespan (link bound and prefixes, as ever) with that many.
+// The count is the smallest whose *thread-bound* end is within 0.1 % of the
+// best: what a lone lane shortens is the chain that runs last, while the
+// makespan's other term, bytes over the link, falls with every further lone
+// lane (files start later, their prefixes grow) although each one gives up a
+// thread's second chain, which max(link, threads) does not price.  Measured
+// on configs[1] (profiles/lone_lane/): the makespan's own minimum, lone = 3,
+// ran no faster than lone = 0 (1,184-1,188 against 1,187-1,192 ms), the
+// thread-bound minimum, lone = 1, ran 1,171-1,174 ms.  And only where the
+// chain can matter: a thread-bound end under 0.9 x the makespan (the model's
+// rates are good to a few per cent) leaves the lanes as they are.
+static constexpr uint64_t kLoneMax = 8;
+static double host_lone_pick(const uint64_t* lens, uint64_t n, HostSchedParams hs, uint64_t lo, uint64_t hi,
+                             uint64_t* lone_out) {
+    std::vector<double> m, te;
+    double best = 1e300;
+    for (uint64_t l = lo; l <= hi; ++l) {
+        hs.lone = l;
+        const HostSched s = host_schedule(lens, n, hs);
+        m.push_back(s.makespan);
+        te.push_back(s.thread_end);
+        best = std::min(best, te.back());
+    }
+    uint64_t pick = 0;
+    if (lo == 0 && te[0] < 0.9 * m[0]) best = te[0];  // the link sets the step by far: no lone lane
+    while (te[pick] > best * 1.001) ++pick;
+    *lone_out = lo + pick;
+    return m[pick];
+}
+
 // The feed rate the planner prices the host leg's HBM-resident bytes at:
 // the context's last measurement at the current width (a whole leg's bytes
 // over its wall time: the D2H copies and the SHA-NI threads together), else
@@ -456,10 +489,13 @@ extern "C" int rf_host_link(rf_ctx* ctx, double* bytes_per_s, int* measured) {
 // With a schedule model (hs: prefix hand-over on), host(h) is instead the
 // thread-aware replay of the pool (host_sched.h) with each message's expected
 // prefix taken off its bytes (the waves' caps are sized by the caller).
-// Without one the split is exactly the per-slot model above.
+// Without one the split is exactly the per-slot model above.  host(h) is
+// priced with the count of lone lanes host_lone_pick chooses for those h
+// messages in lone_lo .. lone_hi; the count for the chosen h goes to *lone_out.
 static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, std::vector<uint32_t>& order,
                        uint32_t n_cu, uint32_t flags, const HostModel& hm, uint32_t* n_host_out,
-                       uint32_t* n_solo_out, const HostSchedParams* hs = nullptr) {
+                       uint32_t* n_solo_out, const HostSchedParams* hs = nullptr, uint64_t lone_lo = 0,
+                       uint64_t lone_hi = 0, uint64_t* lone_out = nullptr) {
     const uint64_t n = nb.size();
     order.resize(n);
     std::iota(order.begin(), order.end(), 0u);
@@ -476,13 +512,14 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
         std::vector<double> host_t(n + 1, hs ? -1.0 : 0.0);
         std::vector<double> load(hm.slots, 0.0);  // min-heap of slot loads (s)
         double maxload = 0, bytes = 0;
-        std::vector<uint64_t> slens;
+        std::vector<uint64_t> slens, lone_at(n + 1, 0);
         if (hs) {
             slens.resize(n);
             for (uint64_t i = 0; i < n; ++i) slens[i] = lens[order[i]];
         }
         auto host_at = [&](uint64_t x) {
-            if (host_t[x] < 0) host_t[x] = x ? host_schedule(slens.data(), x, *hs).makespan : 0.0;
+            if (host_t[x] < 0)
+                host_t[x] = x ? host_lone_pick(slens.data(), x, *hs, lone_lo, lone_hi, &lone_at[x]) : 0.0;
             return host_t[x];
         };
         for (uint64_t i = 0; i < n && !hs; ++i) {
@@ -545,6 +582,10 @@ static void plan_split(const std::vector<uint64_t>& nb, const uint64_t* lens, st
         if (hs && h > 0) {
             const double base = host_at(h);
             while (h < n && gpu_t(h) > 0.9 * base && host_at(h + 1) <= 1.005 * base) ++h;
+        }
+        if (hs && h > 0 && lone_out) {
+            host_at(h);
+            *lone_out = lone_at[h];
         }
     }
     uint64_t k = 0;
@@ -681,7 +722,20 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
         hs.end_frac = 1.0;
         hs.loss_blocks = ckpt / 2;
     }
-    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo, prefix_on ? &hs : nullptr);
+    // Lone lanes: for the plans that get prefixes (the schedule model prices
+    // the split), lone = 0 .. min(threads, kLoneMax) as the model has it;
+    // RF_SHA_LONE=<k> forces k (0: none) on any HBM-resident two-leg plan
+    // with the two-lane chain kernel -- the tests' handle.
+    const bool lone_ok = !host_resident && threads > 0 && ways > 1 &&
+                         !(flags & (RF_SHA_ALL_HOST | RF_SHA_NO_HOST | RF_SHA_ONE_LANE_CHAIN));
+    uint64_t lone_lo = 0, lone_hi = lone_ok && prefix_on ? std::min<uint64_t>(threads, kLoneMax) : 0, lone = 0;
+    if (const char* v = getenv("RF_SHA_LONE")) {
+        const long long k = atoll(v);
+        ARG(k >= 0, "RF_SHA_LONE: a count of messages");
+        lone_lo = lone_hi = lone = lone_ok ? (uint64_t)k : 0;
+    }
+    plan_split(nb, lens, order, (uint32_t)ctx->n_cu, flags, hm, &n_host, &n_solo, prefix_on ? &hs : nullptr, lone_lo,
+               lone_hi, &lone);
     if (prefix_on && n_host) {
         // the caps: what a wave may hash if the host comes late
         std::vector<uint64_t> slens(n_host);
@@ -689,6 +743,7 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
         HostSchedParams hc = hs;
         hc.alpha = hs.alpha > 0 ? kPrefixCapAlpha : 0.0;
         hc.loss_blocks = 0;
+        hc.lone = lone;
         prefix = host_schedule(slens.data(), n_host, hc).prefix_blocks;
     }
     p->flags = flags;
@@ -698,6 +753,8 @@ static int plan_setup(rf_ctx* ctx, rf_sha_plan* p, const uint64_t* offs, const u
     p->n_lanes = (uint32_t)(n - n_solo - n_host);
     p->host.resize(n_host);
     for (uint32_t i = 0; i < n_host; ++i) p->host[i] = HostTask{order[i], offs[order[i]], lens[order[i]]};
+    p->n_lone = (uint32_t)std::min<uint64_t>(lone, n_host);
+    for (uint32_t i = 0; i < p->n_lone; ++i) p->host[i].lone = true;
     // The lanes kernel is persistent: enough 256-thread blocks for every lane
     // message, capped at 5 blocks per CU (its VGPR-limited residency).
     const uint64_t want = (p->n_lanes + sha_lanes_block() - 1) / sha_lanes_block();
@@ -922,6 +979,7 @@ extern "C" int rf_sha_plan_prefix_stats(rf_sha_plan* p, rf_sha_prefix_stats* out
     out->taken = p->pfx_last.taken;
     out->missed = p->pfx_last.missed;
     out->skipped_bytes = p->pfx_last.skipped_bytes;
+    out->n_lone = p->n_lone;
     return RF_OK;
 }
 

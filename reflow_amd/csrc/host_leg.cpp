@@ -168,10 +168,15 @@ namespace {
 // GPU -- whole blocks either way -- so every chunk but the last is whole
 // blocks; len counts from there, total is the message's length):
 // from HBM through the lane's double buffer, or straight from host memory.
+// A lone message read from HBM, once its thread's other lanes are empty,
+// goes through the ring instead (`slot` in host_leg_run): chunk c + 2 is
+// queued when chunk c has arrived, so two copies are in flight while a third
+// chunk is hashed.  rb is the chunk that was current when the ring began
+// (-1: the ring began with the message).
 struct Lane {
-    bool active = false, ready = false;
+    bool active = false, ready = false, ring = false;
     uint64_t task = 0, len = 0, total = 0, nch = 0, c = 0, pos = 0;
-    int buf = 0;
+    int64_t rb = 0;
     const uint8_t* src = nullptr;
     uint32_t st[8];
 };
@@ -187,6 +192,9 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
     const int W = host_ways();
     const uint64_t C = host_chunk_bytes();
     std::vector<double> tw(pool.size(), 0.0), th(pool.size(), 0.0), tt(pool.size(), 0.0);
+    // timing: when each thread ended, and its last message to finish
+    std::vector<double> te(pool.size(), 0.0), tl(pool.size(), 0.0);
+    std::vector<uint64_t> il(pool.size(), ~0ull);
     const double t_run = timing ? now_s() : 0;
     auto fail_with = [&](const char* what, hipError_t e) {
         std::lock_guard<std::mutex> lk(emu);
@@ -200,14 +208,39 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
             if (e != hipSuccess) return fail_with("host leg stage: ", e);
         }
         Lane L[4];
+        int lone_k = -1;  // the lane that holds an active lone message
         auto chunk_len = [&](const Lane& x) { return std::min(C, x.len - x.c * C); };
-        auto data = [&](const Lane& x, int k) -> const uint8_t* {
-            return h_arena ? x.src + x.c * C : st->lane[k].buf[x.buf];
+        // Where chunk j of lane k's message lands, and the stream that brings
+        // it.  Double buffer: the lane's own stage, buffer j & 1.  Ring, for
+        // the chunks d = j - rb >= 2 past its beginning: odd d on the lane's
+        // own stream, even d on the next lane's (empty beside a lone message),
+        // each stage's two buffers in turn -- so the three chunks in use at
+        // any time (one hashed, two in flight) sit in three of the four
+        // buffers, and a stream gets chunk j + 2 only after chunk j, its
+        // previous copy, has been waited for.
+        auto slot = [&](const Lane& x, int k, uint64_t j, hipStream_t* s) -> uint8_t* {
+            const int64_t d = (int64_t)j - x.rb;
+            HostPool::LaneStage* l = &st->lane[k];
+            int b = (int)(j & 1);
+            if (x.ring && d >= 2) {
+                if (d & 1) {
+                    b = (int)((x.rb + 1 + (d - 1) / 2) & 1);
+                } else {
+                    l = &st->lane[(k + 1) % W];
+                    b = (int)((d / 2 - 1) & 1);
+                }
+            }
+            if (s) *s = l->s;
+            return l->buf[b];
         };
-        auto issue = [&](Lane& x, int k, uint64_t c, int b) -> bool {
+        auto data = [&](const Lane& x, int k) -> const uint8_t* {
+            return h_arena ? x.src + x.c * C : slot(x, k, x.c, nullptr);
+        };
+        auto issue = [&](Lane& x, int k, uint64_t c) -> bool {
             const uint64_t off = c * C;
-            const hipError_t e = hipMemcpyAsync(st->lane[k].buf[b], x.src + off, std::min(C, x.len - off),
-                                                hipMemcpyDeviceToHost, st->lane[k].s);
+            hipStream_t s = nullptr;
+            uint8_t* dst = slot(x, k, c, &s);
+            const hipError_t e = hipMemcpyAsync(dst, x.src + off, std::min(C, x.len - off), hipMemcpyDeviceToHost, s);
             if (e != hipSuccess) fail_with("host leg D2H: ", e);
             return e == hipSuccess;
         };
@@ -215,6 +248,7 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
         auto claim = [&](int k) {
             Lane& x = L[k];
             x.active = false;
+            if (lone_k >= 0 && lone_k != k) return;  // beside a lone message: stay empty
             for (uint64_t i; !bad.load(std::memory_order_relaxed) && (i = next.fetch_add(1)) < n;) {
                 x.task = i;
                 x.total = tasks[i].len;
@@ -249,9 +283,21 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                 }
                 x.nch = (x.len + C - 1) / C;
                 x.c = x.pos = 0;
-                x.buf = 0;
                 x.ready = h_arena != nullptr;
-                if (!h_arena && !issue(x, k, 0, 0)) return;
+                x.ring = false;
+                x.rb = 0;
+                if (tasks[i].lone && W > 1) {
+                    lone_k = k;
+                    // alone on the thread already: the ring from chunk 0
+                    bool alone = !h_arena;
+                    for (int o = 0; o < W; ++o) alone = alone && (o == k || !L[o].active);
+                    if (alone) {
+                        x.ring = true;
+                        x.rb = -1;
+                    }
+                }
+                if (!h_arena && !issue(x, k, 0)) return;
+                if (x.ring && x.nch > 1 && !issue(x, k, 1)) return;
                 x.active = true;
                 return;
             }
@@ -268,11 +314,24 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                 Lane& x = L[idx[a]];
                 if (x.ready) continue;
                 const double t0 = timing ? now_s() : 0;
-                const hipError_t e = hipStreamSynchronize(st->lane[idx[a]].s);
+                hipStream_t s = nullptr;
+                slot(x, idx[a], x.c, &s);
+                const hipError_t e = hipStreamSynchronize(s);
                 if (timing) tw[w] += now_s() - t0;
                 if (e != hipSuccess) return fail_with("host leg D2H: ", e);
                 x.ready = true;
-                if (x.c + 1 < x.nch && !issue(x, idx[a], x.c + 1, x.buf ^ 1)) return;
+                const uint64_t nx = x.c + (x.ring ? 2 : 1);
+                if (nx < x.nch && !issue(x, idx[a], nx)) return;
+            }
+            // A lone message whose partner lanes have run empty meanwhile goes
+            // over to the ring: every copy of theirs has been waited for, its
+            // own chunk c is here and c + 1 is queued on its own stream, so
+            // c + 2 can go to the next lane's.
+            if (!h_arena && lone_k >= 0 && na == 1 && !L[lone_k].ring) {
+                Lane& x = L[lone_k];
+                x.ring = true;
+                x.rb = (int64_t)x.c;
+                if (x.c + 2 < x.nch && !issue(x, lone_k, x.c + 2)) return;
             }
             // whole blocks every active lane has left in its current chunk
             uint64_t m = ~0ull;
@@ -291,6 +350,7 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                 host_sha_blocks_multi(na, sp, pp, m);
                 for (int a = 0; a < na; ++a) L[idx[a]].pos += 64 * m;
             }
+            bool lone_ended = false;
             for (int a = 0; a < na; ++a) {
                 Lane& x = L[idx[a]];
                 const uint64_t cl = chunk_len(x);
@@ -298,16 +358,29 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
                 if (x.c + 1 < x.nch) {           // on to the next chunk (its copy is queued)
                     ++x.c;
                     x.pos = 0;
-                    x.buf ^= 1;
                     x.ready = h_arena != nullptr;
                 } else {  // the tail: pad, finish, take the next message
                     host_sha_final(x.st, data(x, idx[a]) + x.pos, cl - x.pos, x.total, out32 + 32 * x.task);
+                    if (timing) {
+                        tl[w] = now_s();
+                        il[w] = x.task;
+                    }
+                    if (lone_k == idx[a]) {
+                        lone_k = -1;
+                        lone_ended = true;
+                    }
                     claim(idx[a]);
                 }
             }
+            // the lanes that stayed empty beside a lone message claim again
+            for (int k = 0; k < W && lone_ended; ++k)
+                if (!L[k].active) claim(k);
             if (timing) th[w] += now_s() - t1;
         }
-        if (timing) tt[w] = now_s() - t_start;
+        if (timing) {
+            te[w] = now_s();
+            tt[w] = te[w] - t_start;
+        }
     });
     if (stats) {
         stats->taken = taken.load();
@@ -315,21 +388,29 @@ bool host_leg_run(HostPool& pool, const HostTask* tasks, uint64_t n, const uint8
         stats->skipped_bytes = skipped.load();
     }
     if (timing) {
-        double sw = 0, sh = 0, mx = 0;
+        double sw = 0, sh = 0, mx = 0, end = 0, idle = 0, t_last = 0;
+        uint64_t last = ~0ull;
         for (unsigned w = 0; w < pool.size(); ++w) {
             sw += tw[w];
             sh += th[w];
             mx = std::max(mx, tt[w]);
+            end = std::max(end, te[w]);
+            if (il[w] != ~0ull && tl[w] > t_last) {
+                t_last = tl[w];
+                last = il[w];
+            }
         }
+        for (unsigned w = 0; w < pool.size(); ++w) idle += end - te[w];
         uint64_t bytes = 0;
         for (uint64_t i = 0; i < n; ++i) bytes += tasks[i].len;
         bytes -= skipped.load();  // what the threads hashed
         fprintf(stderr, "[host leg] %u threads x %d ways, %llu msgs, %.2f GB: wall %.1f ms, slowest thread %.1f ms; "
                         "sum wait %.1f ms, sum hash %.1f ms (%.2f GB/s per hashing thread); prefixes taken %llu, "
-                        "missed %llu, %.3f GB skipped\n",
+                        "missed %llu, %.3f GB skipped; sum idle %.1f ms, last to finish: message %lld, %llu bytes\n",
                 pool.size(), W, (unsigned long long)n, bytes / 1e9, (now_s() - t_run) * 1e3, mx * 1e3, sw * 1e3,
                 sh * 1e3, sh > 0 ? bytes / sh / 1e9 : 0.0, (unsigned long long)taken.load(),
-                (unsigned long long)missed.load(), skipped.load() / 1e9);
+                (unsigned long long)missed.load(), skipped.load() / 1e9, idle * 1e3,
+                last == ~0ull ? -1ll : (long long)last, (unsigned long long)(last == ~0ull ? 0 : tasks[last].len));
     }
     return !bad.load();
 }

@@ -43,7 +43,10 @@ class HostPool {
     // One per interleaved message ("lane") of a thread: a stream and two
     // buffers (chunk c+1's D2H lands in one while chunk c is hashed from the
     // other; one stream suffices because c+1 is queued only after c is
-    // waited on).
+    // waited on).  A lone message (HostTask::lone) borrows the empty lane's
+    // stage beside its own: four buffers, two streams, still never more
+    // than one copy queued on a stream, so hipStreamSynchronize still means
+    // "this chunk has arrived" and no marker is needed.
     struct LaneStage {
         hipStream_t s = nullptr;
         uint8_t* buf[2] = {nullptr, nullptr};
@@ -96,6 +99,12 @@ struct HostTask {
     // still never waits.
     const PrefixRecord* rec = nullptr;
     uint32_t* claimed = nullptr;
+    // Lone lane (host_sched.h, DESIGN.md §5 "Lone lanes"): while a thread
+    // holds this message its other lanes claim nothing (one that is running
+    // finishes its message first), so the chain runs at the one-lane rate.
+    // Read from HBM it then keeps two copies in flight: the thread's two
+    // LaneStages as one ring of four buffers over their two streams.
+    bool lone = false;
 };
 
 // One look at a record: the latest intact slot into st / *blocks.  False:

@@ -15,7 +15,9 @@ struct Thread {
     double t = 0.0;
     double rem[4] = {0, 0, 0, 0};  // bytes left per lane (the per-message cost folded in)
     bool act[4] = {false, false, false, false};
+    uint64_t msg[4] = {0, 0, 0, 0};
     int na = 0;
+    int lone = -1;  // the lane that holds a lone message
 };
 
 // One replay of the pool; prefixes longer than cap_blocks are cut to it.
@@ -27,14 +29,25 @@ uint64_t replay(const uint64_t* lens, uint64_t n, const HostSchedParams& p, uint
     out->prefix_blocks.assign(n, 0);
     out->skipped_bytes = 0.0;
     out->makespan = 0.0;
+    out->t_end.assign(n, -1.0);
+    out->thread.assign(n, ~0u);
+    out->lane.assign(n, 0);
+    out->claims = 0;
+    out->thread_end = 0.0;
     if (!n || !p.threads) return 0;
     const double msg_bytes = p.msg_cost * p.lane_rate[W - 1];
     uint64_t next = 0, longest = 0;
     double cross = 0.0;
+    std::vector<Thread> ths(p.threads);
     auto claim = [&](Thread& th, int k) {
         th.act[k] = false;
+        if (th.lone >= 0 && th.lone != k) return;  // beside a lone message: stay empty
         if (next >= n) return;
         const uint64_t i = next++;
+        if (i < p.lone && W > 1) th.lone = k;
+        out->thread[i] = (uint32_t)(&th - ths.data());
+        out->lane[i] = (uint8_t)k;
+        ++out->claims;
         uint64_t pb = 0;
         if (prefixes) {
             pb = std::min<uint64_t>((uint64_t)std::floor(p.alpha * th.t / p.t_duo), lens[i] / 64);
@@ -49,10 +62,10 @@ uint64_t replay(const uint64_t* lens, uint64_t n, const HostSchedParams& p, uint
         const double left = (double)(lens[i] - 64 * pb);
         cross += left;
         th.rem[k] = left + msg_bytes;
+        th.msg[k] = i;
         th.act[k] = true;
         ++th.na;
     };
-    std::vector<Thread> ths(p.threads);
     // (finish time of the thread's next lane, thread)
     typedef std::pair<double, unsigned> Ev;
     std::priority_queue<Ev, std::vector<Ev>, std::greater<Ev>> q;
@@ -79,16 +92,26 @@ uint64_t replay(const uint64_t* lens, uint64_t n, const HostSchedParams& p, uint
             if (th.act[k]) m = std::min(m, th.rem[k]);
         th.t = t;
         end = std::max(end, t);
+        bool lone_ended = false;
         for (int k = 0; k < W; ++k) {
             if (!th.act[k]) continue;
             th.rem[k] -= m;
             if (th.rem[k] <= 1e-6) {  // done (and any lane that ties with it)
                 --th.na;
+                out->t_end[th.msg[k]] = t;
+                if (th.lone == k) {
+                    th.lone = -1;
+                    lone_ended = true;
+                }
                 claim(th, k);
             }
         }
+        // the lanes that stayed empty beside a lone message claim again
+        for (int k = 0; k < W && lone_ended; ++k)
+            if (!th.act[k]) claim(th, k);
         push(w);
     }
+    out->thread_end = end;
     out->makespan = std::max(end, p.link > 0 ? cross / p.link : 0.0) + p.wake;
     return longest;
 }

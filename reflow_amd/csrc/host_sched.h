@@ -34,6 +34,12 @@ struct HostSchedParams {
     // on average half a checkpoint interval behind the wave -- blocks taken
     // off every prefix (0: the wave's own stopping point, as planned lengths are)
     uint64_t loss_blocks = 0;
+    // lone lanes: the first `lone` messages of the queue run alone on their
+    // thread.  The thread that claims one claims nothing into its other lanes
+    // until that message ends (lanes already running finish their message and
+    // then stay empty), so the message runs at lane_rate[0]; afterwards the
+    // thread claims normally again.  0, or ways == 1: none.
+    uint64_t lone = 0;
 };
 
 struct HostSched {
@@ -41,6 +47,12 @@ struct HostSched {
     std::vector<uint64_t> prefix_blocks;  // whole 64-byte blocks the GPU hashes first
     double makespan = 0.0;                // s, link bound and wake included
     double skipped_bytes = 0.0;           // 64 x sum of prefix_blocks
+    // the replay's own record (of the last replay, like the rest)
+    std::vector<double> t_end;       // s after the pool woke, per message (-1: never ran)
+    std::vector<uint32_t> thread;    // the thread that claimed it (~0u: none did)
+    std::vector<uint8_t> lane;       // ... and into which of its lanes
+    uint64_t claims = 0;             // messages handed out, all told
+    double thread_end = 0.0;         // s: the last thread's end, without link bound and wake
 };
 
 // Messages lens[0..n) in queue order.

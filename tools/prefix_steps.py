@@ -41,9 +41,9 @@ def main():
     pa.close()
     plan = ctx.sha_plan(offs, lens, args.flags)
     st, ps = plan.stats(), plan.prefix_stats()
-    print("split: %d host, %d duo, %d lane; %d prefixed, %.3f GB planned; feed %.2f GB/s"
-          % (st.n_host, st.n_solo, len(lens) - st.n_host - st.n_solo, ps.n_prefixed, ps.planned_bytes / 1e9,
-             ctx.host_link()[0] / 1e9))
+    print("split: %d host (%d lone), %d duo, %d lane; %d prefixed, %.3f GB planned; feed %.2f GB/s"
+          % (st.n_host, ps.n_lone, st.n_solo, len(lens) - st.n_host - st.n_solo, ps.n_prefixed,
+             ps.planned_bytes / 1e9, ctx.host_link()[0] / 1e9))
     rows = []
     for i in range(args.warmup + args.steps):
         t0 = time.perf_counter()
@@ -68,7 +68,7 @@ def main():
                       "skipped_gb_min": round(float(r[:, 6].min()) / 1e9, 3),
                       "skipped_gb_max": round(float(r[:, 6].max()) / 1e9, 3),
                       "planned_gb": round(ps.planned_bytes / 1e9, 3),
-                      "n_prefixed": int(ps.n_prefixed), "host_bytes_gb": round(st.host_bytes / 1e9, 3)}))
+                      "n_prefixed": int(ps.n_prefixed), "n_lone": int(ps.n_lone), "host_bytes_gb": round(st.host_bytes / 1e9, 3)}))
     plan.close()
 
 
