@@ -1238,6 +1238,85 @@ int rf_repo_need_transfer(rf_repo *r, rf_liveset *l, const uint32_t *nodes, uint
 int rf_repo_need_transfer_device(rf_repo *r, rf_liveset *l, const void *d_nodes, uint64_t n_nodes,
                                  rf_repo_missing_out *o, void *stream);
 
+/* ---- Repository index: listing, collect with names, compaction, save / restore
+ * What reads the set back out of HBM.  The reference's Collect exists to
+ * os.Remove every object the liveset does not contain
+ * (repository/file/repository.go:304-327), and a repository outlives the run
+ * that filled it (a directory of objects, repository.go:29-47): the index has
+ * to name what it dropped and to be carried across processes, as the assoc is
+ * (rf_assoc_scan / _compact / _save / _restore above).
+ *
+ * scan: the live objects, each exactly once, in ascending slot order -- IDs as
+ * rows of 32 B and sizes; either array may be NULL.  Tombstones and empty
+ * slots are not listed.  An unchanged table gives equal arrays in both forms
+ * on every call; nothing is promised across histories (which of two colliding
+ * keys of one launch gets the earlier slot is decided by arrival).  The cap
+ * rule of rf_assoc_scan and rf_eval_plan_list: no row at index >= cap is
+ * written, *n is set either way, and the host form returns RF_EINVAL when
+ * *n > cap (the device form's caller compares *d_n with cap).  The device form
+ * is asynchronous on `stream`; a later growth, compaction or destroy waits for
+ * it before it frees the table it reads. */
+int rf_repo_scan(rf_repo *r, uint64_t cap, uint8_t *ids32, int64_t *sizes, uint64_t *n);
+int rf_repo_scan_device(rf_repo *r, uint64_t cap, void *d_ids32, void *d_sizes, void *d_n /* u64 */, void *stream);
+/* Repository.Collect (repository/file/repository.go:304-327) that says what it
+ * removed: rf_repo_collect's rule (live = NULL removes everything; a filter
+ * borrowed from rf_liveset_filter is accepted; the filter's length is read on
+ * the device), and the removed objects' IDs and sizes in ascending slot order,
+ * for the caller's os.Remove (repository.go:316-320).  ALL OR NOTHING: if the
+ * dead objects outnumber `cap` while either list array is given, nothing is
+ * removed and no counter moves; *removed is still set to the number found
+ * (*removed_bytes to 0), the host form returns RF_EINVAL, and the device
+ * form's caller compares *d_removed with cap -- the names of objects that left
+ * the index are never lost.  With both list arrays NULL, cap is ignored and
+ * the call is a plain collect.  Both forms return when applied, as
+ * rf_repo_put_device does; the device form's outputs stay on the device, and
+ * it takes the all-or-nothing decision on the device from the scanned total
+ * (the host form reads the total back once).  rf_repo_stats_get afterwards
+ * shows objects, bytes and tombstones moved by exactly what was listed. */
+int rf_repo_collect_list(rf_repo *r, rf_bloom *live, uint64_t cap, uint8_t *ids32, int64_t *sizes,
+                         uint64_t *removed, int64_t *removed_bytes);
+int rf_repo_collect_list_device(rf_repo *r, rf_bloom *live, uint64_t cap, void *d_ids32, void *d_sizes,
+                                void *d_removed /* u64 */, void *d_removed_bytes /* i64, may be NULL */,
+                                void *stream);
+/* Rebuild the table without its tombstones (a GC pass leaves one per removed
+ * object, and every later probe walks over them until the next growth):
+ * slots = the smallest power of two >= max(RF_REPO_MIN_SLOTS, 2 * max(objects,
+ * min_capacity)), rf_repo_new's rule.  Afterwards tombstones == 0 and rebuilds
+ * is one higher; every Stat, Put, Remove, missing and need_transfer answers as
+ * before the call. */
+int rf_repo_compact(rf_repo *r, uint64_t min_capacity);
+/* The index across processes: a new process restores the file instead of
+ * walking the object directory and Stat-ing every object
+ * (repository/file/repository.go:93-101) before its first missing().
+ * save writes the live objects to `path` (beside it first, then renamed);
+ * restore checks the whole file on the host before a kernel sees a byte --
+ * RF_EINVAL for a file that is not one (magic, version, flags, reserved
+ * bytes, sizes, truncation) or whose entries break the rules below,
+ * RF_EINTEGRITY for a checksum mismatch (errors.Integrity,
+ * repository.go:160-162), RF_EIO if it cannot be opened or read; *out is then
+ * untouched and the context stays usable -- and bulk-loads a table of
+ * rf_repo_new(entries)'s slots: objects and bytes from the file, tombstones,
+ * rebuilds and the last_* fields zero.
+ * File, little-endian: header 64 B (magic "RFREPO01", u32 version = 1, u32
+ * flags = 0, u64 n_entries <= 2^30, u64 chunk > 0, i64 total_bytes = the sum of
+ * the sizes, 24 zero bytes); n_entries entries of 40 B (32-B ID, i64 size >=
+ * 0), strictly ascending by ID bytes, so equal contents give equal files
+ * whatever the table's history; one SHA-256 per `chunk` bytes of the entry
+ * area (the last chunk may be short); SHA-256(header || those digests); the
+ * end marker "RFREEND1". */
+int rf_repo_save(rf_repo *r, const char *path);
+int rf_repo_restore(rf_ctx *ctx, const char *path, rf_repo **out);
+/* The file form on the host alone (no device), as rf_assoc_file_format /
+ * _parse: chunk = checksum granule in bytes (0 = 64 MiB); the entries are
+ * given in file order.  *out_len = bytes needed (RF_EINVAL when cap is
+ * short); *n = the file's entries (RF_EINVAL with *n set when cap_entries is
+ * short).  parse applies every check of rf_repo_restore and never reads past
+ * len. */
+int rf_repo_file_format(const uint8_t *ids32, const int64_t *sizes, uint64_t n, uint64_t chunk,
+                        uint8_t *out, uint64_t cap, uint64_t *out_len);
+int rf_repo_file_parse(const uint8_t *buf, uint64_t len, uint8_t *ids32, int64_t *sizes,
+                       uint64_t cap_entries, uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

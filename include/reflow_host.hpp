@@ -794,8 +794,22 @@ class RepoIndex {
     // once to list.  A caller that can bound the list calls rf_repo_need_transfer itself, once.
     Report NeedTransfer(GcLiveset& l, const std::vector<uint32_t>& nodes);
     rf_repo_stats Stats();
+    // The live objects, each once, in ascending slot order (rf_repo_scan).
+    using Object = std::pair<Digest, int64_t>;
+    std::vector<Object> List();
+    // Repository.Collect that names what it removed (repository/file/repository.go:304-327: the caller's
+    // os.Remove per object), in ascending slot order; nothing is removed unless all of it is listed.
+    std::vector<Object> CollectList(const GcLiveset& live);
+    std::vector<Object> CollectAllList();  // a nil liveset
+    // Rebuild without tombstones at the slots of max(objects, min_capacity) (rf_repo_compact).
+    void Compact(uint64_t min_capacity = 0);
+    // The index across processes (rf_repo_save / rf_repo_restore): a checksummed file of the live objects.
+    void Save(const std::string& path);
+    static std::unique_ptr<RepoIndex> Restore(Engine& e, const std::string& path);
 
    private:
+    RepoIndex() = default;  // (Restore)
+    std::vector<Object> CollectListWith(rf_bloom* live);
     rf_repo* r_ = nullptr;
 };
 

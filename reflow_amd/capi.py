@@ -95,6 +95,8 @@ EXPORTS = [
     "rf_repo_new", "rf_repo_destroy", "rf_repo_put", "rf_repo_put_device", "rf_repo_remove",
     "rf_repo_remove_device", "rf_repo_stat", "rf_repo_stat_device", "rf_repo_collect", "rf_repo_stats_get",
     "rf_repo_missing", "rf_repo_missing_device", "rf_repo_need_transfer", "rf_repo_need_transfer_device",
+    "rf_repo_scan", "rf_repo_scan_device", "rf_repo_collect_list", "rf_repo_collect_list_device",
+    "rf_repo_compact", "rf_repo_save", "rf_repo_restore", "rf_repo_file_format", "rf_repo_file_parse",
 ]
 
 
@@ -523,6 +525,14 @@ def lib():
             "rf_repo_missing_device": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
             "rf_repo_need_transfer": ([vp, vp, vp, u64, vp], i32),
             "rf_repo_need_transfer_device": ([vp, vp, vp, u64, vp, vp], i32),
+            "rf_repo_scan": ([vp, u64, vp, vp, vp], i32), "rf_repo_scan_device": ([vp, u64, vp, vp, vp, vp], i32),
+            "rf_repo_collect_list": ([vp, vp, u64, vp, vp, vp, vp], i32),
+            "rf_repo_collect_list_device": ([vp, vp, u64, vp, vp, vp, vp, vp], i32),
+            "rf_repo_compact": ([vp, u64], i32),
+            "rf_repo_save": ([vp, ctypes.c_char_p], i32),
+            "rf_repo_restore": ([vp, ctypes.c_char_p, vp], i32),
+            "rf_repo_file_format": ([vp, vp, u64, u64, vp, u64, vp], i32),
+            "rf_repo_file_parse": ([vp, u64, vp, vp, u64, vp], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -1946,6 +1956,67 @@ class Repo:
     def need_transfer_device(self, liveset, d_nodes, n_nodes, out: RepoMissingOut, stream=None):
         _check(lib().rf_repo_need_transfer_device(self._h, liveset._h, d_nodes, n_nodes, ctypes.byref(out), stream))
 
+    @staticmethod
+    def _list_out(cap, ids, sizes, poison):
+        """Host arrays of `cap` rows for a list (None where not wanted), filled with the byte `poison`."""
+        a = np.full((max(cap, 1), 32), poison, dtype=np.uint8) if ids else None
+        b = np.frombuffer(bytes([poison]) * (8 * max(cap, 1)), dtype=np.int64).copy() if sizes else None
+        return a, b
+
+    def scan(self, cap=None, ids=True, sizes=True, poison=0, check=True):
+        """rf_repo_scan: (ids [cap, 32] or None, sizes [cap] or None, n, rc) --
+        the live objects in ascending slot order in the first min(n, cap) rows.
+        cap: rows of the arrays (default: the live count, the arrays then cut to
+        n).  check=False returns the cap rule's RF_EINVAL in rc instead of raising."""
+        full = cap is None
+        cap = self.stats().objects if full else int(cap)
+        a, b = self._list_out(cap, ids, sizes, poison)
+        n = ctypes.c_uint64()
+        rc = lib().rf_repo_scan(self._h, cap, _ptr(a), _ptr(b), ctypes.byref(n))
+        if check:
+            _check(rc)
+        keep = n.value if full else cap
+        return (a[:keep] if a is not None else None, b[:keep] if b is not None else None, n.value, rc)
+
+    def scan_device(self, cap, d_ids32, d_sizes, d_n, stream=None):
+        _check(lib().rf_repo_scan_device(self._h, cap, d_ids32, d_sizes, d_n, stream))
+
+    def collect_list(self, live=None, cap=None, ids=True, sizes=True, poison=0, check=True):
+        """rf_repo_collect_list: (ids, sizes, removed, removed_bytes, rc) -- the
+        removed objects in ascending slot order; all or nothing against cap
+        (default: the live count, the arrays then cut to `removed`)."""
+        full = cap is None
+        cap = self.stats().objects if full else int(cap)
+        a, b = self._list_out(cap, ids, sizes, poison)
+        n, nb = ctypes.c_uint64(), ctypes.c_int64()
+        rc = lib().rf_repo_collect_list(self._h, live._h if live is not None else None, cap, _ptr(a), _ptr(b),
+                                        ctypes.byref(n), ctypes.byref(nb))
+        if check:
+            _check(rc)
+        keep = n.value if full else cap
+        return (a[:keep] if a is not None else None, b[:keep] if b is not None else None, n.value, nb.value, rc)
+
+    def collect_list_device(self, live, cap, d_ids32, d_sizes, d_removed, d_removed_bytes=None, stream=None):
+        _check(lib().rf_repo_collect_list_device(self._h, live._h if live is not None else None, cap, d_ids32,
+                                                 d_sizes, d_removed, d_removed_bytes, stream))
+
+    def compact(self, min_capacity=0):
+        """rf_repo_compact: rebuild the table without its tombstones."""
+        _check(lib().rf_repo_compact(self._h, min_capacity))
+
+    def save(self, path):
+        """rf_repo_save: the live objects as a checksummed file (restore())."""
+        _check(lib().rf_repo_save(self._h, os.fsencode(path)))
+
+    @classmethod
+    def restore(cls, ctx, path):
+        """rf_repo_restore: a new index holding a saved file's objects."""
+        r = cls.__new__(cls)
+        r.ctx = ctx
+        r._h = ctypes.c_void_p()
+        _check(lib().rf_repo_restore(ctx.handle, os.fsencode(path), ctypes.byref(r._h)))
+        return r
+
     def close(self):
         if self._h:
             lib().rf_repo_destroy(self._h)
@@ -1985,3 +2056,48 @@ def assoc_file_parse(buf: bytes):
     vals = np.zeros((max(n.value, 1), 32), dtype=np.uint8)
     _check(lib().rf_assoc_file_parse(_ptr(b), len(b), _ptr(kinds), _ptr(keys), _ptr(vals), n.value, ctypes.byref(n)))
     return kinds[:n.value], keys[:n.value], vals[:n.value]
+
+
+def repo_file_format(ids32, sizes, chunk=0, cap=None) -> bytes:
+    """rf_repo_file_format (host only): the index file of objects given in ID
+    order.  cap: the output buffer's bytes (default: what the file needs); a
+    short one raises RfError(RF_EINVAL) with .needed = the file's length."""
+    ids = np.ascontiguousarray(ids32, dtype=np.uint8).reshape(-1)
+    sz = np.ascontiguousarray(sizes, dtype=np.int64)
+    n = len(sz)
+    assert len(ids) == 32 * n
+    need = ctypes.c_uint64()
+    if cap is None:
+        lib().rf_repo_file_format(_ptr(ids), _ptr(sz), n, chunk, None, 0, ctypes.byref(need))  # the size
+        cap = need.value
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    rc = lib().rf_repo_file_format(_ptr(ids), _ptr(sz), n, chunk, _ptr(out), cap, ctypes.byref(need))
+    if rc != RF_OK:
+        err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+        err.needed = need.value
+        raise err
+    return out[:need.value].tobytes()
+
+
+def repo_file_parse(buf: bytes, cap_entries=None):
+    """rf_repo_file_parse (host only): (ids [n, 32], sizes int64 [n]) of an
+    index file; RfError RF_EINVAL / RF_EINTEGRITY for a bad one.  cap_entries:
+    the arrays' rows (default: the file's); a short one raises
+    RfError(RF_EINVAL) with .needed = the file's entries."""
+    b = np.frombuffer(bytes(buf), dtype=np.uint8)
+    n = ctypes.c_uint64()
+    if cap_entries is None:
+        rc = lib().rf_repo_file_parse(_ptr(b) if len(b) else None, len(b), None, None, 0, ctypes.byref(n))
+        if rc != RF_OK and not (rc == RF_EINVAL and n.value):
+            _check(rc)
+        cap_entries = n.value
+    ids = np.zeros((max(cap_entries, 1), 32), dtype=np.uint8)
+    sizes = np.zeros(max(cap_entries, 1), dtype=np.int64)
+    n = ctypes.c_uint64()
+    rc = lib().rf_repo_file_parse(_ptr(b) if len(b) else None, len(b), _ptr(ids), _ptr(sizes), cap_entries,
+                                  ctypes.byref(n))
+    if rc != RF_OK:
+        err = RfError(rc, lib().rf_last_error().decode(errors="replace"))
+        err.needed = n.value
+        raise err
+    return ids[:n.value], sizes[:n.value]

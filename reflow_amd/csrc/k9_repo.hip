@@ -619,7 +619,211 @@ __global__ __launch_bounds__(kRepoBlock) void k9_list_scatter(RepoRows r, const 
     }
 }
 
+// ---- the index read back: scan, collect with names, bulk load ----------------------
+// A tile is kRepoListTile slots, one workgroup, four slots a lane (slot counts
+// are powers of two >= 1024: tiles are whole).  The lane's 4-bit mask of slots
+// whose tag is live:
+__device__ __forceinline__ uint32_t repo_live_mask(const uint32_t* __restrict__ tag, uint64_t first) {
+    const uint4 t = *reinterpret_cast<const uint4*>(tag + first);
+    return (t.x == kRepoTagLive ? 1u : 0u) | (t.y == kRepoTagLive ? 2u : 0u) | (t.z == kRepoTagLive ? 4u : 0u) |
+           (t.w == kRepoTagLive ? 8u : 0u);
+}
+
+// the block's sum of one figure per lane into tile_count[blockIdx.x]
+__device__ __forceinline__ void repo_tile_total(uint32_t v, uint32_t* __restrict__ tile_count) {
+    __shared__ uint32_t s_cnt[kRepoBlock / 64];
+    const uint32_t cnt = repo_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < kRepoBlock / 64; ++k) c += s_cnt[k];
+        tile_count[blockIdx.x] = c;
+    }
+}
+
+// the rank of the lane's first marked slot: the tile's offset, the waves before (LDS) and the lanes before
+__device__ __forceinline__ uint64_t repo_tile_rank(uint64_t tile_off, uint32_t c) {
+    __shared__ uint32_t s_w[kRepoBlock / 64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = c;  // inclusive wave scan
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= (uint32_t)o) x += y;
+    }
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    uint64_t rank = tile_off + (x - c);
+    for (uint32_t k = 0; k < wave; ++k) rank += s_w[k];
+    return rank;
+}
+
+__device__ __forceinline__ void repo_write_row(const RepoView& t, uint64_t q, uint64_t rank,
+                                               uint8_t* __restrict__ out_ids, long long* __restrict__ out_sizes) {
+    if (out_ids) {
+        uint4* o = reinterpret_cast<uint4*>(out_ids + 32ull * rank);
+        o[0] = t.keys[2 * q];
+        o[1] = t.keys[2 * q + 1];
+    }
+    if (out_sizes) out_sizes[rank] = t.size[q];
+}
+
+// Scan 1/3: live tags per tile.
+__global__ __launch_bounds__(kRepoBlock) void k9_index_count(RepoView t, uint32_t* __restrict__ tile_count) {
+    const uint64_t first = ((uint64_t)blockIdx.x * kRepoBlock + threadIdx.x) * 4;
+    repo_tile_total((uint32_t)__builtin_popcount(repo_live_mask(t.tag, first)), tile_count);
+}
+
+// Scan 3/3 (after launch_repo_scan over the tile counts): per tile, ascending slot; ranks below cap are written.
+__global__ __launch_bounds__(kRepoBlock) void k9_index_scatter(RepoView t, const uint64_t* __restrict__ tile_off,
+                                                               uint64_t cap, uint8_t* __restrict__ out_ids,
+                                                               long long* __restrict__ out_sizes) {
+    const uint64_t base = tile_off[blockIdx.x];
+    if (base >= cap) return;  // uniform over the block
+    const uint64_t first = ((uint64_t)blockIdx.x * kRepoBlock + threadIdx.x) * 4;
+    const uint32_t m = repo_live_mask(t.tag, first);
+    uint64_t rank = repo_tile_rank(base, (uint32_t)__builtin_popcount(m));
+    for (uint32_t q = m; q && rank < cap; q &= q - 1, ++rank)
+        repo_write_row(t, first + (uint32_t)__builtin_ctz(q), rank, out_ids, out_sizes);
+}
+
+// Collect with names 1/3, the mark: a slot is dead when it is live and the
+// filter does not hold its ID (or there is no filter).  The filter is probed
+// here, once per object; nothing is removed.  dead: a byte per slot.
+__global__ __launch_bounds__(kRepoBlock) void k9_collect_mark(RepoView t, bool all,
+                                                              const uint64_t* __restrict__ words,
+                                                              const uint64_t* __restrict__ len_dev, uint64_t m,
+                                                              uint64_t mu, uint32_t k, uint8_t* __restrict__ dead,
+                                                              uint32_t* __restrict__ tile_count) {
+    const uint64_t length = all ? 0 : *len_dev;
+    const uint64_t first = ((uint64_t)blockIdx.x * kRepoBlock + threadIdx.x) * 4;
+    const uint32_t live = repo_live_mask(t.tag, first);
+    uint32_t bytes4 = 0, c = 0;
+    for (uint32_t q = live; q; q &= q - 1) {
+        const uint32_t j = (uint32_t)__builtin_ctz(q);
+        if (!all && bloom_contains(words, length, m, mu, k, reinterpret_cast<const uint8_t*>(&t.keys[2 * (first + j)])))
+            continue;
+        bytes4 |= 1u << (8 * j);
+        ++c;
+    }
+    *reinterpret_cast<uint32_t*>(dead + first) = bytes4;
+    repo_tile_total(c, tile_count);
+}
+
+// Collect with names 3/3, the apply (after launch_repo_scan over the tile
+// counts): all or nothing on the scanned total, read from device memory by
+// every workgroup alike.  The dead slots become tombstones, their rows go to
+// their ranks, and the counters move as k9_collect moves them: a fixed grid
+// that strides over the tiles, one add per wave and word at the end (a
+// workgroup per tile adding as it goes is 2.6M adds to five addresses at 2^25
+// slots: the call measured 8.5 ms that way and 1.3 ms this way).
+__global__ __launch_bounds__(kRepoBlock) void k9_collect_apply(RepoView t, uint64_t tiles,
+                                                               const uint8_t* __restrict__ dead,
+                                                               const uint64_t* __restrict__ tile_off,
+                                                               const uint64_t* __restrict__ total, uint64_t cap,
+                                                               uint8_t* __restrict__ out_ids,
+                                                               long long* __restrict__ out_sizes) {
+    if (*total > cap) return;  // uniform over the grid: nothing is removed, no counter moves
+    uint64_t objs = 0, bytes = 0;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {  // (uniform over the block)
+        const uint64_t first = (tile * kRepoBlock + threadIdx.x) * 4;
+        const uint32_t m = repo_tile_mask(dead, first);
+        const uint32_t c = (uint32_t)__builtin_popcount(m);
+        uint64_t rank = repo_tile_rank(tile_off[tile], c);
+        for (uint32_t q = m; q; q &= q - 1, ++rank) {
+            const uint64_t slot = first + (uint32_t)__builtin_ctz(q);
+            if (rank < cap) repo_write_row(t, slot, rank, out_ids, out_sizes);
+            t.tag[slot] = kRepoTagTomb;
+            bytes += (uint64_t)t.size[slot];
+        }
+        objs += c;
+        __syncthreads();  // the next tile reuses the waves' sums in LDS
+    }
+    const uint64_t o = repo_wave_sum64(objs), b = repo_wave_sum64(bytes);
+    if ((threadIdx.x & 63) == 0 && o) {
+        atomicAdd(&t.ctr[kRepoGone], (unsigned long long)o);
+        atomicAdd(&t.ctr[kRepoGoneBytes], (unsigned long long)b);
+        atomicAdd(&t.ctr[kRepoObjects], (unsigned long long)((uint64_t)0 - o));
+        atomicAdd(&t.ctr[kRepoBytes], (unsigned long long)((uint64_t)0 - b));
+        atomicAdd(&t.ctr[kRepoTombs], (unsigned long long)o);
+    }
+}
+
+// Bulk load 1/2 (rf_repo_restore): n dense objects with DISTINCT IDs (the
+// file's order was checked on the host) claim a slot of the empty table `to` --
+// k9_rebuild's protocol, no dedup pass; k9_rebuild_publish is 2/2.
+__global__ __launch_bounds__(kRepoBlock) void k9_load(const uint8_t* __restrict__ ids,
+                                                      const long long* __restrict__ sizes, uint64_t n, RepoView to) {
+    bool bad = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * kRepoBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kRepoBlock) {
+        const uint4* d = reinterpret_cast<const uint4*>(ids + 32ull * i);
+        const uint4 lo = d[0], hi = d[1];
+        uint32_t slot = key_hash(lo, hi) & to.mask;
+        uint32_t probes = 0;
+        for (;; ++probes) {
+            if (probes >= kRepoMaxProbe) {
+                bad = true;
+                break;
+            }
+            if (atomicCAS(&to.tag[slot], kRepoTagEmpty, kRepoTagBusy) == kRepoTagEmpty) {
+                to.keys[2 * slot] = lo;
+                to.keys[2 * slot + 1] = hi;
+                to.size[slot] = sizes[i];
+                break;
+            }
+            slot = (slot + 1) & to.mask;
+        }
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&to.ctr[kRepoFlags], (unsigned long long)kRepoFlagProbe);
+}
+
 // ---- launches ----------------------------------------------------------------------
+hipError_t launch_repo_index_count(const RepoView& t, uint64_t slots, uint32_t* tile_count, uint64_t* tile_sums,
+                                   uint64_t* tile_off, uint64_t* d_total, hipStream_t s) {
+    const uint64_t tiles = slots / kRepoListTile;
+    hipLaunchKernelGGL(k9_index_count, dim3((uint32_t)tiles), dim3(kRepoBlock), 0, s, t, tile_count);
+    return launch_repo_scan(tile_count, tiles, tile_sums, tile_off, d_total, s);
+}
+
+hipError_t launch_repo_index_scatter(const RepoView& t, uint64_t slots, const uint64_t* tile_off, uint64_t cap,
+                                     uint8_t* out_ids, int64_t* out_sizes, hipStream_t s) {
+    if (!cap || !(out_ids || out_sizes)) return hipSuccess;
+    hipLaunchKernelGGL(k9_index_scatter, dim3((uint32_t)(slots / kRepoListTile)), dim3(kRepoBlock), 0, s, t, tile_off,
+                       cap, out_ids, reinterpret_cast<long long*>(out_sizes));
+    return hipGetLastError();
+}
+
+hipError_t launch_repo_collect_mark(const RepoView& t, uint64_t slots, const BloomDev* live, uint8_t* dead,
+                                    uint32_t* tile_count, uint64_t* tile_sums, uint64_t* tile_off, uint64_t* d_total,
+                                    hipStream_t s) {
+    hipError_t e = hipMemsetAsync(t.ctr + kRepoGone, 0, 16, s);
+    if (e != hipSuccess) return e;
+    const uint64_t tiles = slots / kRepoListTile;
+    const bool all = live == nullptr;
+    hipLaunchKernelGGL(k9_collect_mark, dim3((uint32_t)tiles), dim3(kRepoBlock), 0, s, t, all,
+                       all ? nullptr : live->words, all ? nullptr : live->len_dev, all ? 1ull : live->m,
+                       all || !live->m ? 0ull : (~0ull) / live->m, all ? 0u : (uint32_t)live->k, dead, tile_count);
+    return launch_repo_scan(tile_count, tiles, tile_sums, tile_off, d_total, s);
+}
+
+hipError_t launch_repo_collect_apply(const RepoView& t, uint64_t slots, const uint8_t* dead, const uint64_t* tile_off,
+                                     const uint64_t* d_total, uint64_t cap, uint8_t* out_ids, int64_t* out_sizes,
+                                     hipStream_t s) {
+    const uint64_t tiles = slots / kRepoListTile;  // a fixed grid that strides: one add per wave and counter word
+    hipLaunchKernelGGL(k9_collect_apply, dim3((uint32_t)std::min<uint64_t>(tiles, 2048)), dim3(kRepoBlock), 0, s, t,
+                       tiles, dead, tile_off, d_total, cap, out_ids, reinterpret_cast<long long*>(out_sizes));
+    return hipGetLastError();
+}
+
+hipError_t launch_repo_load(const uint8_t* ids, const int64_t* sizes, uint64_t n, const RepoView& to,
+                            uint64_t to_slots, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k9_load, dim3(repo_grid(n)), dim3(kRepoBlock), 0, s, ids, reinterpret_cast<const long long*>(sizes),
+                       n, to);
+    hipLaunchKernelGGL(k9_rebuild_publish, dim3(repo_grid(to_slots)), dim3(kRepoBlock), 0, s, to, to_slots);
+    return hipGetLastError();
+}
+
 hipError_t launch_repo_dedup(const RepoRows& r, hipStream_t s) {
     if (!r.n_rows) return hipSuccess;
     hipError_t e = hipMemsetAsync(r.table, 0xff, 4ull * ((uint64_t)r.mask + 1), s);

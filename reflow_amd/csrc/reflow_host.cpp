@@ -1623,6 +1623,64 @@ std::pair<uint64_t, int64_t> RepoIndex::CollectAll() {
     return {n, bytes};
 }
 
+static std::vector<RepoIndex::Object> repo_objects(const std::vector<Digest>& ids, const std::vector<int64_t>& sizes,
+                                                   uint64_t n) {
+    std::vector<RepoIndex::Object> out(n);
+    for (uint64_t i = 0; i < n; ++i) out[i] = {ids[i], sizes[i]};
+    return out;
+}
+
+std::vector<RepoIndex::Object> RepoIndex::List() {
+    // another thread may Put between the count and the scan: retry with the size the scan reports
+    uint64_t n = Stats().objects;
+    std::vector<Digest> ids;
+    std::vector<int64_t> sizes;
+    for (;;) {
+        const uint64_t cap = n;
+        ids.resize(cap + 1);
+        sizes.resize(cap + 1);
+        const int rc = rf_repo_scan(r_, cap, ids[0].b.data(), sizes.data(), &n);
+        if (rc == RF_EINVAL && n > cap) continue;
+        reflow::Check(rc);
+        break;
+    }
+    return repo_objects(ids, sizes, n);
+}
+
+std::vector<RepoIndex::Object> RepoIndex::CollectListWith(rf_bloom* live) {
+    // all or nothing: a list that is too short removes nothing and reports the room it needs
+    uint64_t n = Stats().objects;
+    std::vector<Digest> ids;
+    std::vector<int64_t> sizes;
+    for (;;) {
+        const uint64_t cap = n;
+        ids.resize(cap + 1);
+        sizes.resize(cap + 1);
+        const int rc = rf_repo_collect_list(r_, live, cap, ids[0].b.data(), sizes.data(), &n, nullptr);
+        if (rc == RF_EINVAL && n > cap) continue;
+        reflow::Check(rc);
+        break;
+    }
+    return repo_objects(ids, sizes, n);
+}
+
+std::vector<RepoIndex::Object> RepoIndex::CollectList(const GcLiveset& live) {
+    if (!live.live_.b_) throw Error(RF_EPRECONDITION, "RepoIndex: the liveset has not been collected yet");
+    return CollectListWith(live.live_.b_);
+}
+
+std::vector<RepoIndex::Object> RepoIndex::CollectAllList() { return CollectListWith(nullptr); }
+
+void RepoIndex::Compact(uint64_t min_capacity) { reflow::Check(rf_repo_compact(r_, min_capacity)); }
+
+void RepoIndex::Save(const std::string& path) { reflow::Check(rf_repo_save(r_, path.c_str())); }
+
+std::unique_ptr<RepoIndex> RepoIndex::Restore(Engine& e, const std::string& path) {
+    std::unique_ptr<RepoIndex> r(new RepoIndex());
+    reflow::Check(rf_repo_restore(e.ctx(), path.c_str(), &r->r_));
+    return r;
+}
+
 // One call with room for every row; the report cut to what was listed.
 template <class Call>
 static RepoIndex::Report repo_report(uint64_t groups, uint64_t cap, bool row_form, Call call) {

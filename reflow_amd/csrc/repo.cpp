@@ -9,17 +9,25 @@
 // table and the object's scratch; it records an event there, and every later
 // call on the object waits for that event before it touches either.
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
+#include <memory>
+#include <numeric>
+#include <string>
 #include <vector>
 
 #include "ctx.h"
 #include "engine.h"
+#include "host_par.h"
 #include "live_internal.h"
 #include "plan_internal.h"  // bloom_ctx, bloom_dev: the filter object behind rf_bloom*, as a fused lookup sees it
 #include "repo_check.h"
 #include "repo_internal.h"
+#include "repo_io.h"
 
 using namespace rf;
 
@@ -34,11 +42,13 @@ struct rf_repo {
     DevBuf b_counts, b_nodes, b_deg, b_bad, b_seg_base, b_seg_group, b_seg_src, b_seg_cnt, b_seg_off, b_tile_sums;
     DevBuf b_row_ord, b_row_src, b_nfiles, b_nmissing, b_mbytes, b_gstatus, b_miss, b_tiles, b_total, b_miss_ptr;
     DevBuf b_lrows, b_lids, b_lsizes;  // the host form's list
+    DevBuf b_itiles, b_ioff, b_dead;   // scan / collect_list: counts and offsets per tile of slots, the dead marks
     std::vector<DevBuf*> scratch() {
         return {&b_ids,     &b_sizes,    &b_status,  &b_removed,  &b_canon,   &b_slot_of,  &b_table,  &b_counts,
                 &b_nodes,   &b_deg,      &b_bad,     &b_seg_base, &b_seg_group, &b_seg_src, &b_seg_cnt, &b_seg_off,
                 &b_tile_sums, &b_row_ord, &b_row_src, &b_nfiles,  &b_nmissing, &b_mbytes,  &b_gstatus, &b_miss,
-                &b_tiles,   &b_total,    &b_miss_ptr, &b_lrows,   &b_lids,    &b_lsizes};
+                &b_tiles,   &b_total,    &b_miss_ptr, &b_lrows,   &b_lids,    &b_lsizes,  &b_itiles,  &b_ioff,
+                &b_dead};
     }
     RepoView view() {
         return RepoView{tag.as<uint32_t>(), keys.as<uint4>(), size.as<long long>(), (uint32_t)(slots - 1),
@@ -618,4 +628,262 @@ extern "C" int rf_repo_need_transfer_device(rf_repo* r, rf_liveset* l, const voi
     in.d_nodes = static_cast<const uint32_t*>(d_nodes);
     in.n_groups = n_nodes;
     return repo_missing_device(r, in, o, false, pick(ctx, stream));
+}
+
+// ---- scan / collect_list / compact -------------------------------------------------
+// the arrays of a pass over the table's tiles
+static int repo_tile_bufs(rf_repo* r) {
+    const uint64_t tiles = r->slots / kRepoListTile;
+    HIPC(r->b_itiles.ensure(4 * tiles));
+    HIPC(r->b_ioff.ensure(8 * (tiles + 1)));
+    HIPC(r->b_tile_sums.ensure(8 * ((tiles + kRepoListTile - 1) / kRepoListTile + 1)));
+    HIPC(r->b_total.ensure(16));
+    return RF_OK;
+}
+
+// the first w rows of the host form's staging to the caller's arrays
+static int repo_rows_to_host(rf_repo* r, uint64_t w, uint8_t* ids32, int64_t* sizes, hipStream_t s) {
+    if (w && ids32) HIPC(hipMemcpyAsync(ids32, r->b_lids.p, 32 * w, hipMemcpyDeviceToHost, s));
+    if (w && sizes) HIPC(hipMemcpyAsync(sizes, r->b_lsizes.p, 8 * w, hipMemcpyDeviceToHost, s));
+    return RF_OK;
+}
+static int repo_stage_rows(rf_repo* r, uint64_t w, bool ids, bool sizes) {
+    if (w && ids) HIPC(r->b_lids.ensure(32 * w));
+    if (w && sizes) HIPC(r->b_lsizes.ensure(8 * w));
+    return RF_OK;
+}
+
+// (context mutex held, device set, quiesced) the live objects counted, then the first min(n, cap) of them staged
+static int repo_scan_locked(rf_repo* r, uint64_t cap, bool ids, bool sizes, uint64_t* n, hipStream_t s) {
+    if (int rc = repo_tile_bufs(r)) return rc;
+    HIPC(launch_repo_index_count(r->view(), r->slots, r->b_itiles.as<uint32_t>(), r->b_tile_sums.as<uint64_t>(),
+                                 r->b_ioff.as<uint64_t>(), r->b_total.as<uint64_t>(), s));
+    if (int rc = repo_read_total(r, n, s)) return rc;
+    const uint64_t w = std::min(*n, cap);
+    if (int rc = repo_stage_rows(r, w, ids, sizes)) return rc;
+    HIPC(launch_repo_index_scatter(r->view(), r->slots, r->b_ioff.as<uint64_t>(), w,
+                                   ids ? r->b_lids.as<uint8_t>() : nullptr, sizes ? r->b_lsizes.as<int64_t>() : nullptr,
+                                   s));
+    return RF_OK;
+}
+
+extern "C" int rf_repo_scan(rf_repo* r, uint64_t cap, uint8_t* ids32, int64_t* sizes, uint64_t* n) {
+    ARG(r && n, "null argument");
+    rf_ctx* ctx = r->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = ctx->stream;
+    if (int rc = repo_scan_locked(r, cap, ids32 != nullptr, sizes != nullptr, n, s)) return rc;
+    if (int rc = repo_rows_to_host(r, std::min(*n, cap), ids32, sizes, s)) return rc;
+    uint64_t c[kRepoCtrWords];
+    if (int rc = repo_read_ctr(r, c, s)) return rc;
+    if (*n > cap) return fail(RF_EINVAL, "list buffers too small: need %llu entries", (unsigned long long)*n);
+    return RF_OK;
+}
+
+extern "C" int rf_repo_scan_device(rf_repo* r, uint64_t cap, void* d_ids32, void* d_sizes, void* d_n, void* stream) {
+    ARG(r && d_n, "null argument");
+    rf_ctx* ctx = r->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if (int rc = repo_tile_bufs(r)) return rc;
+    hipError_t e = launch_repo_index_count(r->view(), r->slots, r->b_itiles.as<uint32_t>(),
+                                           r->b_tile_sums.as<uint64_t>(), r->b_ioff.as<uint64_t>(),
+                                           static_cast<uint64_t*>(d_n), s);
+    if (e == hipSuccess)
+        e = launch_repo_index_scatter(r->view(), r->slots, r->b_ioff.as<uint64_t>(), cap,
+                                      static_cast<uint8_t*>(d_ids32), static_cast<int64_t*>(d_sizes), s);
+    const int rc = repo_mark_reader(r, s);  // (whatever was queued reads the table and the scratch)
+    if (e != hipSuccess) return fail(RF_EDEVICE, "repo scan: %s", hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int rf_repo_collect_list(rf_repo* r, rf_bloom* live, uint64_t cap, uint8_t* ids32, int64_t* sizes,
+                                    uint64_t* removed, int64_t* removed_bytes) {
+    ARG(r, "null argument");
+    if (!ids32 && !sizes) return rf_repo_collect(r, live, removed, removed_bytes, nullptr);
+    rf_ctx* ctx = r->ctx;
+    ARG(!live || bloom_ctx(live) == ctx, "the filter belongs to another context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = ctx->stream;
+    if (int rc = repo_tile_bufs(r)) return rc;
+    HIPC(r->b_dead.ensure(r->slots));
+    HIPC(launch_repo_collect_mark(r->view(), r->slots, live ? &bloom_dev(live) : nullptr, r->b_dead.as<uint8_t>(),
+                                  r->b_itiles.as<uint32_t>(), r->b_tile_sums.as<uint64_t>(), r->b_ioff.as<uint64_t>(),
+                                  r->b_total.as<uint64_t>(), s));
+    uint64_t dead = 0;
+    if (int rc = repo_read_total(r, &dead, s)) return rc;
+    if (removed) *removed = dead;
+    if (removed_bytes) *removed_bytes = 0;
+    if (dead > cap)  // all or nothing: the names of what leaves the index are never lost
+        return fail(RF_EINVAL, "list buffers too small: need %llu entries (nothing was removed)",
+                    (unsigned long long)dead);
+    if (int rc = repo_stage_rows(r, dead, ids32 != nullptr, sizes != nullptr)) return rc;
+    HIPC(launch_repo_collect_apply(r->view(), r->slots, r->b_dead.as<uint8_t>(), r->b_ioff.as<uint64_t>(),
+                                   r->b_total.as<uint64_t>(), dead, ids32 ? r->b_lids.as<uint8_t>() : nullptr,
+                                   sizes ? r->b_lsizes.as<int64_t>() : nullptr, s));
+    if (int rc = repo_rows_to_host(r, dead, ids32, sizes, s)) return rc;
+    uint64_t c[kRepoCtrWords];
+    if (int rc = repo_read_ctr(r, c, s)) return rc;
+    if (removed_bytes) *removed_bytes = (int64_t)c[kRepoGoneBytes];
+    return RF_OK;
+}
+
+extern "C" int rf_repo_collect_list_device(rf_repo* r, rf_bloom* live, uint64_t cap, void* d_ids32, void* d_sizes,
+                                           void* d_removed, void* d_removed_bytes, void* stream) {
+    ARG(r && d_removed, "null argument");
+    rf_ctx* ctx = r->ctx;
+    ARG(!live || bloom_ctx(live) == ctx, "the filter belongs to another context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = pick(ctx, stream);
+    const BloomDev* bd = live ? &bloom_dev(live) : nullptr;
+    uint64_t* ctr = r->ctr.as<uint64_t>();
+    if (!d_ids32 && !d_sizes) {  // a plain collect
+        HIPC(launch_repo_collect(r->view(), r->slots, bd, s));
+        HIPC(hipMemcpyAsync(d_removed, ctr + kRepoGone, 8, hipMemcpyDeviceToDevice, s));
+    } else {
+        if (int rc = repo_tile_bufs(r)) return rc;
+        HIPC(r->b_dead.ensure(r->slots));
+        HIPC(launch_repo_collect_mark(r->view(), r->slots, bd, r->b_dead.as<uint8_t>(), r->b_itiles.as<uint32_t>(),
+                                      r->b_tile_sums.as<uint64_t>(), r->b_ioff.as<uint64_t>(),
+                                      static_cast<uint64_t*>(d_removed), s));
+        HIPC(launch_repo_collect_apply(r->view(), r->slots, r->b_dead.as<uint8_t>(), r->b_ioff.as<uint64_t>(),
+                                       static_cast<const uint64_t*>(d_removed), cap, static_cast<uint8_t*>(d_ids32),
+                                       static_cast<int64_t*>(d_sizes), s));
+    }
+    if (d_removed_bytes) HIPC(hipMemcpyAsync(d_removed_bytes, ctr + kRepoGoneBytes, 8, hipMemcpyDeviceToDevice, s));
+    uint64_t c[kRepoCtrWords];
+    return repo_read_ctr(r, c, s);
+}
+
+extern "C" int rf_repo_compact(rf_repo* r, uint64_t min_capacity) {
+    ARG(r, "null argument");
+    rf_ctx* ctx = r->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = ctx->stream;
+    uint64_t c[kRepoCtrWords];
+    if (int rc = repo_read_ctr(r, c, s)) return rc;
+    uint64_t slots = 0;
+    char msg[160];
+    if (!repo_slots_for(std::max<uint64_t>(c[kRepoObjects], min_capacity), &slots, msg, sizeof msg))
+        return fail(RF_EINVAL, "repo compact: %s", msg);
+    if (int rc = repo_rebuild(r, slots, s)) return rc;
+    return repo_read_ctr(r, c, s);
+}
+
+// ---- save / restore ----------------------------------------------------------------
+namespace {
+struct CFile {
+    FILE* f = nullptr;
+    ~CFile() {
+        if (f) fclose(f);
+    }
+};
+}  // namespace
+
+extern "C" int rf_repo_save(rf_repo* r, const char* path) {
+    ARG(r && path && *path, "null argument");
+    rf_ctx* ctx = r->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    if (int rc = repo_quiesce(r)) return rc;
+    hipStream_t s = ctx->stream;
+    uint64_t n = 0;
+    if (int rc = repo_scan_locked(r, ~0ull, true, true, &n, s)) return rc;
+    std::vector<uint8_t> ids(32 * n);
+    std::vector<int64_t> sizes(n);
+    if (int rc = repo_rows_to_host(r, n, ids.data(), sizes.data(), s)) return rc;
+    uint64_t c[kRepoCtrWords];
+    if (int rc = repo_read_ctr(r, c, s)) return rc;
+    // slot order -> ID order: the file does not depend on the table's history
+    HostPool* pool = ctx_pool(ctx);
+    std::vector<uint32_t> perm(n);
+    std::iota(perm.begin(), perm.end(), 0u);
+    pool_sort(pool, perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+        return memcmp(ids.data() + 32ull * x, ids.data() + 32ull * y, 32) < 0;
+    });
+    std::vector<uint8_t> file(repo_file_bytes(n, kRepoFileChunk));
+    if (int rc = repo_file_write(ids.data(), sizes.data(), perm.data(), n, kRepoFileChunk, file.data(),
+                                 [&](const uint8_t* b, uint64_t len, uint64_t chunk, uint8_t* out) {
+                                     hash_chunks(pool, b, len, chunk, out);
+                                 }))
+        return rc;
+    // a reader never sees a partial file: written beside it, then renamed (rf_assoc_save)
+    const std::string tmp = std::string(path) + ".tmp";
+    CFile out;
+    if (!(out.f = fopen(tmp.c_str(), "wb"))) return fail(RF_EIO, "repo save: cannot create %s", tmp.c_str());
+    if (fwrite(file.data(), 1, file.size(), out.f) != file.size()) return fail(RF_EIO, "repo save: write failed");
+    if (fflush(out.f) != 0 || fsync(fileno(out.f)) != 0) return fail(RF_EIO, "repo save: flush failed");
+    fclose(out.f);
+    out.f = nullptr;
+    if (rename(tmp.c_str(), path) != 0) return fail(RF_EIO, "repo save: cannot rename to %s", path);
+    return RF_OK;
+}
+
+extern "C" int rf_repo_restore(rf_ctx* ctx, const char* path, rf_repo** out) {
+    ARG(ctx && path && out, "null argument");
+    std::vector<uint8_t> file;
+    {
+        CFile in;
+        if (!(in.f = fopen(path, "rb"))) return fail(RF_EIO, "repo restore: cannot open %s", path);
+        struct stat st;
+        if (fstat(fileno(in.f), &st) != 0 || st.st_size < 0) return fail(RF_EIO, "repo restore: cannot stat %s", path);
+        // the largest valid file: 2^30 entries and their checksums
+        if ((uint64_t)st.st_size > repo_file_bytes(kRepoFileMaxEntries, 64))
+            return fail(RF_EINVAL, "repo restore: %s is too large for a repository index file", path);
+        file.resize((size_t)st.st_size);
+        if (!file.empty() && fread(file.data(), 1, file.size(), in.f) != file.size())
+            return fail(RF_EIO, "repo restore: cannot read %s", path);
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DevGuard dg(ctx->device);
+    // everything is checked on the host before any of it reaches a kernel
+    HostPool* pool = ctx_pool(ctx);
+    uint64_t n = 0, slots = 0;
+    int64_t total = 0;
+    if (int rc = repo_file_check(file.data(), file.size(), &n, &total,
+                                 [&](const uint8_t* b, uint64_t len, uint64_t chunk, uint8_t* o) {
+                                     hash_chunks(pool, b, len, chunk, o);
+                                 }))
+        return rc;
+    char msg[160];
+    if (!repo_slots_for(n, &slots, msg, sizeof msg)) return fail(RF_EINVAL, "repo restore: %s", msg);
+    std::vector<uint8_t> ids(32 * n);
+    std::vector<int64_t> sizes(n);
+    repo_file_unpack(file.data(), n, ids.data(), sizes.data());
+    auto* r = new rf_repo();
+    std::unique_ptr<rf_repo, void (*)(rf_repo*)> guard(r, repo_free);
+    r->ctx = ctx;
+    r->device = ctx->device;
+    r->slots = slots;
+    hipStream_t s = ctx->stream;
+    hipError_t e = repo_alloc_table(r->tag, r->keys, r->size, slots, s);
+    if (e == hipSuccess) e = r->ctr.ensure(8 * kRepoCtrWords);
+    if (e == hipSuccess && n) e = r->b_ids.ensure(32 * n);
+    if (e == hipSuccess && n) e = r->b_sizes.ensure(8 * n);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? RF_ENOMEM : RF_EDEVICE, "repo alloc: %s", hipGetErrorString(e));
+    HIPC(hipEventCreateWithFlags(&r->e_reader, hipEventDisableTiming));
+    uint64_t c[kRepoCtrWords] = {};
+    c[kRepoObjects] = n;
+    c[kRepoBytes] = (uint64_t)total;
+    HIPC(hipMemcpyAsync(r->ctr.p, c, sizeof c, hipMemcpyHostToDevice, s));
+    if (n) {
+        HIPC(hipMemcpyAsync(r->b_ids.p, ids.data(), 32 * n, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(r->b_sizes.p, sizes.data(), 8 * n, hipMemcpyHostToDevice, s));
+        HIPC(launch_repo_load(r->b_ids.as<uint8_t>(), r->b_sizes.as<int64_t>(), n, r->view(), slots, s));
+    }
+    if (int rc = repo_read_ctr(r, c, s)) return rc;  // (synchronises: the host arrays are done with)
+    guard.release();
+    *out = r;
+    return RF_OK;
 }

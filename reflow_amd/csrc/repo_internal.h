@@ -87,6 +87,27 @@ hipError_t launch_repo_resolve(const RepoView& t, const RepoRows& r, uint32_t* n
 hipError_t launch_repo_list(const RepoRows& r, const uint8_t* miss, uint32_t* tile_count, uint64_t cap,
                             uint64_t* out_rows, uint8_t* out_ids, int64_t* out_sizes, uint64_t* d_total,
                             hipStream_t s);
+// The live objects in ascending slot order.  count: *d_total = their number and tile_off = the first rank of every
+// tile of kRepoListTile slots (tile_count: [slots / kRepoListTile]; tile_off: one more, u64; tile_sums:
+// launch_repo_scan's).  scatter: ranks below cap get the ID and the size (either may be null).
+hipError_t launch_repo_index_count(const RepoView& t, uint64_t slots, uint32_t* tile_count, uint64_t* tile_sums,
+                                   uint64_t* tile_off, uint64_t* d_total, hipStream_t s);
+hipError_t launch_repo_index_scatter(const RepoView& t, uint64_t slots, const uint64_t* tile_off, uint64_t cap,
+                                     uint8_t* out_ids, int64_t* out_sizes, hipStream_t s);
+// Repository.Collect that lists what it removes, ascending slot order.  mark: dead[slot] = 1 for the objects `live`
+// does not contain (null: all), *d_total = their number, tile_off as above; nothing is removed, and
+// ctr[kRepoGone, kRepoGoneBytes] are zeroed.  apply: if *d_total (device memory) exceeds cap nothing happens --
+// decided on the device; otherwise the dead become tombstones, the counters move as launch_repo_collect moves
+// them, and rank i gets the i-th removed object's ID and size (either may be null).
+hipError_t launch_repo_collect_mark(const RepoView& t, uint64_t slots, const BloomDev* live, uint8_t* dead,
+                                    uint32_t* tile_count, uint64_t* tile_sums, uint64_t* tile_off, uint64_t* d_total,
+                                    hipStream_t s);
+hipError_t launch_repo_collect_apply(const RepoView& t, uint64_t slots, const uint8_t* dead, const uint64_t* tile_off,
+                                     const uint64_t* d_total, uint64_t cap, uint8_t* out_ids, int64_t* out_sizes,
+                                     hipStream_t s);
+// n dense objects with distinct IDs into the empty table `to` (the counters are the caller's)
+hipError_t launch_repo_load(const uint8_t* ids, const int64_t* sizes, uint64_t n, const RepoView& to,
+                            uint64_t to_slots, hipStream_t s);
 // status[g] = bad[g] (int32)
 hipError_t launch_repo_copy_status(const uint32_t* bad, int32_t* status, uint64_t n_groups, hipStream_t s);
 
