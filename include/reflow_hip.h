@@ -330,6 +330,66 @@ int rf_fileset_marshal_json(const rf_fileset_tree *t, uint32_t root, uint8_t *ou
 int rf_fileset_value_digest_batch(rf_ctx *ctx, const rf_fileset_tree *t, const uint32_t *roots,
                                   uint64_t n, uint8_t *out32);
 
+/* ---- Fileset values marshalled on the device (Eval.CacheWrite's marshal(fs),
+ * eval.go:1141 -> eval.go:1961-1967 = json.Marshal + Repository.Put) ----------
+ * The bytes of rf_fileset_marshal_json, made in HBM for a batch of values whose
+ * File IDs may already be there (the out32 of K1 over the installed files,
+ * local/executor.go:514-557).  The host flattens each root into a piece stream
+ * in output order -- literal pieces (skeleton bytes such as {"List":[ , ]
+ * "Fileset":{ }, held once in a small blob) and entry pieces (one Map entry and
+ * a bit for its comma), the entries of a Map ordered bytewise (Maps already in
+ * order are found in one linear pass and left alone) -- in O(fileset nodes +
+ * entries) plus that sort.  The device measures the pieces, scans tiles of
+ * RF_MARSHAL_TILE pieces (tile mark / scan / scatter, no atomic on a shared
+ * counter) and emits every value at a 16-byte aligned offset of one arena (K1
+ * wants offs % 16 == 0), pad bytes zeroed.  The value lengths and a "zero ID
+ * seen" word are read back once; the JSON stays in HBM.  Refusals are those of
+ * rf_fileset_marshal_json with its status (a node out of range, a CSR that is
+ * not monotone, a depth above 4096, duplicate map keys, a zero ID); a batch
+ * whose JSON could reach 4 GiB is refused with RF_EINVAL (split it). */
+#define RF_MARSHAL_TILE 1024 /* pieces per tile of the marshal's length / scan / emit */
+typedef struct rf_json_batch rf_json_batch;
+/* Host only, no context, not a product path: the piece stream of roots[0 .. n)
+ * run through the per-piece code the kernels run, so that CPU tests cover
+ * flatten, sort and emit.  Value i's bytes at out + offs[i], offs[n] = *out_len
+ * = the bytes needed (RF_EINVAL, nothing written, if cap is short); offs may be
+ * NULL. */
+int rf_fileset_marshal_flat(const rf_fileset_tree *t, const uint32_t *roots, uint64_t n, uint8_t *out,
+                            uint64_t cap, uint64_t *offs /* n + 1 */, uint64_t *out_len);
+/* json.Marshal of roots[0 .. n) into a batch object.  d_ids32 != NULL: entry
+ * e's File ID is device row e (16-byte aligned) and t->ids32 may be NULL; a
+ * zero ID is then found on the device.  Either way a zero ID fails the call
+ * with RF_EINVAL and leaves *out untouched.  Returns when the bytes are
+ * written. */
+int rf_fileset_marshal_device(rf_ctx *ctx, const rf_fileset_tree *t, const uint32_t *roots, uint64_t n,
+                              const void *d_ids32 /* or NULL: t->ids32 */, rf_json_batch **out, void *stream);
+/* Values, the sum of their JSON lengths, and pieces; any pointer may be NULL. */
+int rf_json_batch_info(const rf_json_batch *b, uint64_t *n, uint64_t *total_bytes, uint64_t *n_pieces);
+/* Where the marshal call spent its time, host clock, milliseconds: ms[0]
+ * flatten + sort on the host, ms[1] upload + length pass + scan + the
+ * read-back, ms[2] arena setup + emit pass (each ends in a synchronise). */
+int rf_json_batch_times(const rf_json_batch *b, double ms[3]);
+/* lens[i] = bytes of value i: the Size Repository.Put reports (repository.go:108-114). */
+int rf_json_batch_lens(const rf_json_batch *b, int64_t *lens);
+/* The arena, the values' offsets (u64 [n], each % 16 == 0) and their lengths
+ * (i64 [n]) as device pointers, valid until rf_json_batch_free. */
+int rf_json_batch_device(const rf_json_batch *b, const void **d_arena, const void **d_offs, const void **d_lens);
+/* D2H copy of the values which[0 .. n) (NULL: values 0 .. n-1), packed: value j
+ * at out + offs[j], offs[n] = the bytes needed (set either way; RF_EINVAL if
+ * cap is short) -- for the caller's real Repository.Put of the bytes. */
+int rf_json_batch_copy(rf_json_batch *b, const uint64_t *which, uint64_t n, uint8_t *out, uint64_t cap,
+                       uint64_t *offs /* n + 1 */);
+/* d_out32[i] = SHA256(value i): the fsid (eval.go:1141-1151).  K1 over the
+ * arena through the one-shot plan of rf_sha256_batch, GPU legs only.  Returns
+ * when done. */
+int rf_json_batch_digests_device(rf_json_batch *b, void *d_out32, void *stream);
+void rf_json_batch_free(rf_json_batch *b);
+/* Marshal plus digests in one call, the device twin of
+ * rf_fileset_value_digest_batch: d_out32[i] = the fsid of roots[i], d_sizes[i]
+ * (i64, may be NULL) = its JSON length. */
+int rf_fileset_value_digest_device(rf_ctx *ctx, const rf_fileset_tree *t, const uint32_t *roots, uint64_t n,
+                                   const void *d_ids32, void *d_out32, void *d_sizes, void *stream);
+
 /* ---- Coalescing concurrent callers (SURVEY §8(b) "Threading") -----------
  * The reference digests files in <=60 goroutines (local/executor.go:41,
  * 522-538) and looks cache keys up in a goroutine per node (eval.go:402-411);
@@ -1316,6 +1376,47 @@ int rf_repo_file_format(const uint8_t *ids32, const int64_t *sizes, uint64_t n, 
                         uint8_t *out, uint64_t cap, uint64_t *out_len);
 int rf_repo_file_parse(const uint8_t *buf, uint64_t len, uint8_t *ids32, int64_t *sizes,
                        uint64_t cap_entries, uint64_t *n);
+
+/* ---- The cache write (Eval.CacheWrite, eval.go:1113-1154) --------------------
+ * What the plan and the waves later look up, written by one call: after
+ * rf_eval_wave_step, the nodes that RAN and whose value is a Fileset
+ * (eval.go:1119-1130) are listed with their fsids (SHA-256 of the value's JSON,
+ * rf_json_batch_digests_device) and JSON lengths, row i of d_fsids32 (16-byte
+ * aligned) / d_sizes belonging to nodes[i].  Accepted hits are not listed: the
+ * reference repairs those through rf_assoc_repair.  Every listed node must be
+ * DONE in the wave object (RF_EINVAL otherwise, nothing touched); a node listed
+ * twice takes part twice, in order.
+ *   Node i takes part iff it is flagged RF_PLAN_F_CACHEABLE, is not
+ * (no_cache_extern and RF_PLAN_F_EXTERN) (eval.go:1131) and has at least one
+ * present key -- keys as they are now, from g's slots through key_slots or from
+ * d_keys32, by rf_eval_wave_step's rule: a row of 32 zero bytes is absent
+ * (flow.go:798-800); with g, RF_EPRECONDITION while an input change is pending.
+ * RF_PLAN_F_INVALID does not matter for a write.
+ *   Each participating node contributes Put(zero expect, key, fsid) for each of
+ * its present keys (eval.go:1146-1152): one batch, node order then key order,
+ * through rf_assoc_put_device's insert path, so "ops on one key apply in index
+ * order" decides duplicates the same way on every run.  With repo, each
+ * participating node's (fsid, JSON length) is Put into the index first (marshal
+ * = Repository.Put, eval.go:1961-1967), first-wins as rf_repo_put_device.
+ * Growth of either table is decided on the host before the kernels.  The call
+ * holds the context's lock, every object of one context (RF_EINVAL), and
+ * returns when applied.
+ * Out of scope: Transferer.Transfer (eval.go:1138) is I/O -- the caller runs
+ * rf_repo_need_transfer / rf_repo_missing against the destination index first;
+ * values that are not Filesets; dep.Err. */
+typedef struct {
+    uint64_t size;                  /* = sizeof(rf_cache_write_out), set by the caller */
+    uint64_t nodes_written;         /* listed nodes that took part */
+    uint64_t keys_put;              /* their present keys: the Puts */
+    uint64_t skipped_not_cacheable; /* listed nodes skipped, by the first reason that holds */
+    uint64_t skipped_extern;
+    uint64_t skipped_no_key;
+    uint8_t *node_keys;             /* host, [n] or NULL (set by the caller): keys put for nodes[i] */
+} rf_cache_write_out;
+int rf_eval_wave_cache_write(rf_eval_wave *w, const uint32_t *nodes, uint64_t n, const void *d_fsids32,
+                             const void *d_sizes /* int64, JSON lengths */, int no_cache_extern, rf_graph *g,
+                             const void *d_keys32, rf_assoc *a, int kind, rf_repo *repo /* may be NULL */,
+                             rf_cache_write_out *o /* may be NULL */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ RF_LIVE_ROUND_BATCH = 4
 RF_REPO_MAX_ROWS = 1 << 30
 RF_REPO_MIN_SLOTS = 1024
 RF_REPO_LIST_TILE = 1024
+# device marshal of Fileset values (rf_fileset_marshal_device): pieces per tile
+RF_MARSHAL_TILE = 1024
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -97,6 +99,9 @@ EXPORTS = [
     "rf_repo_missing", "rf_repo_missing_device", "rf_repo_need_transfer", "rf_repo_need_transfer_device",
     "rf_repo_scan", "rf_repo_scan_device", "rf_repo_collect_list", "rf_repo_collect_list_device",
     "rf_repo_compact", "rf_repo_save", "rf_repo_restore", "rf_repo_file_format", "rf_repo_file_parse",
+    "rf_fileset_marshal_flat", "rf_fileset_marshal_device", "rf_json_batch_info", "rf_json_batch_times", "rf_json_batch_lens",
+    "rf_json_batch_device", "rf_json_batch_copy", "rf_json_batch_digests_device", "rf_json_batch_free",
+    "rf_fileset_value_digest_device", "rf_eval_wave_cache_write",
 ]
 
 
@@ -195,6 +200,102 @@ def fileset_marshal_json(fs) -> bytes:
     out = ctypes.create_string_buffer(max(need.value, 1))
     _check(lib().rf_fileset_marshal_json(ctypes.byref(t), root, out, need.value, ctypes.byref(need)))
     return out.raw[:need.value]
+
+
+def fileset_marshal_flat(sets):
+    """json.Marshal of each fileset through the piece stream and the per-piece
+    code the marshal kernels run (host code, no device): a list of bytes."""
+    b = FilesetTreeBuilder()
+    roots = np.array([b.add(fs) for fs in sets], dtype=np.uint32)
+    t = b.struct()
+    n = len(sets)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    need = ctypes.c_uint64(0)
+    rc = lib().rf_fileset_marshal_flat(ctypes.byref(t), _ptr(roots) if n else None, n, None, 0, _ptr(offs),
+                                       ctypes.byref(need))
+    if rc != RF_OK and need.value == 0:
+        _check(rc)
+    out = np.zeros(max(need.value, 1), dtype=np.uint8)
+    _check(lib().rf_fileset_marshal_flat(ctypes.byref(t), _ptr(roots) if n else None, n, _ptr(out), need.value,
+                                         _ptr(offs), ctypes.byref(need)))
+    assert int(offs[n]) == need.value
+    return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+
+class JsonBatch:
+    """rf_json_batch: Fileset values marshalled to JSON in device memory."""
+
+    def __init__(self, ctx, sets=None, tree=None, roots=None, d_ids32=None, stream=None):
+        """sets: fileset objects (FilesetTreeBuilder.add), or tree + roots: an
+        rf_fileset_tree struct and its root nodes.  d_ids32: the File IDs as
+        device rows, entry e's at row e; the tree's own IDs are then not read."""
+        self.ctx = ctx
+        if sets is not None:
+            b = FilesetTreeBuilder()
+            roots = [b.add(fs) for fs in sets]
+            tree = b.struct()
+            self._keep = b
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        self._h = ctypes.c_void_p()
+        _check(lib().rf_fileset_marshal_device(ctx.handle, ctypes.byref(tree), _ptr(r) if len(r) else None, len(r),
+                                               d_ids32, ctypes.byref(self._h), stream))
+        n, total, pieces = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().rf_json_batch_info(self._h, ctypes.byref(n), ctypes.byref(total), ctypes.byref(pieces)))
+        self.n, self.total_bytes, self.n_pieces = n.value, total.value, pieces.value
+
+    def times(self):
+        """(flatten + sort, upload + length + scan + read-back, arena + emit) of the marshal call, ms."""
+        ms = (ctypes.c_double * 3)()
+        _check(lib().rf_json_batch_times(self._h, ms))
+        return tuple(ms)
+
+    def lens(self) -> np.ndarray:
+        out = np.zeros(max(self.n, 1), dtype=np.int64)
+        _check(lib().rf_json_batch_lens(self._h, _ptr(out)))
+        return out[:self.n]
+
+    def device(self):
+        """(arena, offs, lens) device pointers."""
+        a, o, l = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _check(lib().rf_json_batch_device(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.byref(l)))
+        return a.value, o.value, l.value
+
+    def copy(self, which=None):
+        """The chosen values' bytes (default: all), a list of bytes."""
+        w = None if which is None else np.ascontiguousarray(which, dtype=np.uint64)
+        n = self.n if w is None else len(w)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        rc = lib().rf_json_batch_copy(self._h, _ptr(w) if w is not None and n else None, n, None, 0, _ptr(offs))
+        if rc != RF_OK and int(offs[n]) == 0:
+            _check(rc)
+        out = np.zeros(max(int(offs[n]), 1), dtype=np.uint8)
+        _check(lib().rf_json_batch_copy(self._h, _ptr(w) if w is not None and n else None, n, _ptr(out), int(offs[n]),
+                                        _ptr(offs)))
+        return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    def digests_device(self, d_out32, stream=None):
+        _check(lib().rf_json_batch_digests_device(self._h, d_out32, stream))
+
+    def digests(self) -> list:
+        """The fsids on the host (a device buffer and a download; for tests)."""
+        if not self.n:
+            return []
+        d = self.ctx.alloc(32 * self.n)
+        self.digests_device(d.ptr)
+        out = d.to_numpy(np.uint8, 32 * self.n)
+        d.free()
+        return [out[32 * i:32 * i + 32].tobytes() for i in range(self.n)]
+
+    def close(self):
+        if self._h:
+            lib().rf_json_batch_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GraphPart(ctypes.Structure):
@@ -327,6 +428,13 @@ class RepoStats(ctypes.Structure):
     _fields_ = [("objects", ctypes.c_uint64), ("bytes", ctypes.c_int64), ("tombstones", ctypes.c_uint64),
                 ("capacity", ctypes.c_uint64), ("rebuilds", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
                 ("last_rows", ctypes.c_uint64), ("last_files", ctypes.c_uint64), ("last_missing", ctypes.c_uint64)]
+
+
+class CacheWriteOut(ctypes.Structure):
+    """rf_cache_write_out: what one rf_eval_wave_cache_write call did."""
+    _fields_ = [("size", ctypes.c_uint64), ("nodes_written", ctypes.c_uint64), ("keys_put", ctypes.c_uint64),
+                ("skipped_not_cacheable", ctypes.c_uint64), ("skipped_extern", ctypes.c_uint64),
+                ("skipped_no_key", ctypes.c_uint64), ("node_keys", ctypes.c_void_p)]
 
 
 class RepoMissingOut(ctypes.Structure):
@@ -533,6 +641,15 @@ def lib():
             "rf_repo_restore": ([vp, ctypes.c_char_p, vp], i32),
             "rf_repo_file_format": ([vp, vp, u64, u64, vp, u64, vp], i32),
             "rf_repo_file_parse": ([vp, u64, vp, vp, u64, vp], i32),
+            "rf_fileset_marshal_flat": ([vp, vp, u64, vp, u64, vp, vp], i32),
+            "rf_fileset_marshal_device": ([vp, vp, vp, u64, vp, vp, vp], i32),
+            "rf_json_batch_info": ([vp, vp, vp, vp], i32), "rf_json_batch_lens": ([vp, vp], i32),
+            "rf_json_batch_times": ([vp, vp], i32),
+            "rf_json_batch_device": ([vp, vp, vp, vp], i32),
+            "rf_json_batch_copy": ([vp, vp, u64, vp, u64, vp], i32),
+            "rf_json_batch_digests_device": ([vp, vp, vp], i32), "rf_json_batch_free": ([vp], None),
+            "rf_fileset_value_digest_device": ([vp, vp, vp, u64, vp, vp, vp, vp], i32),
+            "rf_eval_wave_cache_write": ([vp, vp, u64, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -774,6 +891,26 @@ class Context:
         _check(lib().rf_fileset_value_digest_batch(self._h, ctypes.byref(t), _ptr(roots), len(sets),
                                                    _ptr(out)))
         return [out[32 * i:32 * i + 32].tobytes() for i in range(len(sets))]
+
+    def fileset_value_digests_device(self, sets, d_ids32=None):
+        """The same through the device marshal (rf_fileset_value_digest_device):
+        (fsids, JSON lengths).  d_ids32: the File IDs as device rows."""
+        if not sets:
+            return [], np.zeros(0, np.int64)
+        b = FilesetTreeBuilder()
+        roots = np.array([b.add(fs) for fs in sets], dtype=np.uint32)
+        t = b.struct()
+        n = len(sets)
+        d_out, d_sz = self.alloc(32 * n), self.alloc(8 * n)
+        try:
+            _check(lib().rf_fileset_value_digest_device(self._h, ctypes.byref(t), _ptr(roots), n, d_ids32, d_out.ptr,
+                                                        d_sz.ptr, None))
+            out = d_out.to_numpy(np.uint8, 32 * n)
+            sizes = d_sz.to_numpy(np.int64, n)
+        finally:
+            d_out.free()
+            d_sz.free()
+        return [out[32 * i:32 * i + 32].tobytes() for i in range(n)], sizes
 
 
 class ShaStreams:
@@ -1654,6 +1791,21 @@ class EvalWave:
     def reject(self, nodes):
         nd = np.ascontiguousarray(nodes, dtype=np.uint32)
         _check(lib().rf_eval_wave_reject(self._h, _ptr(nd) if len(nd) else None, len(nd)))
+
+    def cache_write(self, nodes, d_fsids32, d_sizes, assoc, kind, graph=None, d_keys=None, repo=None,
+                    no_cache_extern=False, per_node=True, stream=None):
+        """rf_eval_wave_cache_write: the listed (DONE) nodes' values, row i of
+        d_fsids32 / d_sizes for nodes[i], Put under every present key and into
+        the repository index.  Returns (CacheWriteOut, keys put per listed node)."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        o = CacheWriteOut()
+        o.size = ctypes.sizeof(o)
+        per = np.zeros(max(len(nd), 1), dtype=np.uint8) if per_node else None
+        o.node_keys = _ptr(per)
+        _check(lib().rf_eval_wave_cache_write(self._h, _ptr(nd) if len(nd) else None, len(nd), d_fsids32, d_sizes,
+                                              int(bool(no_cache_extern)), self._h_of(graph), d_keys, assoc._h, kind,
+                                              self._h_of(repo), ctypes.byref(o), stream))
+        return o, (per[:len(nd)] if per_node else None)
 
     def states(self) -> np.ndarray:
         out = np.zeros(max(self.n, 1), dtype=np.uint8)

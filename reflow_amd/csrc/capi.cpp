@@ -37,6 +37,7 @@
 #include "host_sched.h"
 #include "ctx.h"
 #include "assoc_io.h"
+#include "cwrite_internal.h"
 #include "graph_internal.h"
 #include "host_par.h"
 #include "host_sha.h"
@@ -100,6 +101,8 @@ extern "C" void rf_destroy(rf_ctx* ctx) {
     ctx->d_tab2.release();
     ctx->d_tab3.release();
     ctx->d_place.release();
+    ctx->d_cw.release();
+    ctx->d_cw2.release();
     ctx->h_stage.release();
     ctx->sc_dedup.destroy();
     ctx->sc_collect.destroy();
@@ -1046,6 +1049,17 @@ static int sha_device_packed(rf_ctx* ctx, const std::vector<uint64_t>& offs, con
         if (e != hipSuccess) rc = fail(RF_EDEVICE, "sha256 batch: %s", hipGetErrorString(e));
     }
     return rc;
+}
+
+// Messages resident in device memory (a JSON batch's arena): the context's
+// one-shot plan set up for device-resident messages, GPU legs only -- the bytes
+// are not in host memory and a host leg would fetch them over the link.
+int rf::sha_resident_locked(rf_ctx* ctx, const void* d_arena, const uint64_t* offs, const uint64_t* lens, uint64_t n,
+                            void* d_out32, hipStream_t s) {
+    if (!n) return RF_OK;
+    if (!ctx->tplan) ctx->tplan = new rf_sha_plan();
+    if (int rc = plan_setup(ctx, ctx->tplan, offs, lens, n, RF_SHA_NO_HOST, false)) return rc;
+    return plan_run_locked(ctx->tplan, d_arena, d_out32, s);
 }
 
 // Host-buffer batch packed in the pinned stage: plan first, upload only the
@@ -3127,6 +3141,13 @@ static int assoc_put_locked(rf_assoc* a, int kind, const uint8_t* d_exp, const u
         std::swap(rem, next);
     }
     return RF_OK;
+}
+
+int rf::assoc_put_rows_locked(rf_assoc* a, int kind, const uint8_t* d_keys, const uint8_t* d_vals, uint64_t n,
+                              int32_t* d_status) {
+    ARG(n <= (1u << 30), "assoc batch too large");
+    if (!n) return RF_OK;
+    return assoc_put_locked(a, kind, nullptr, d_keys, d_vals, n, d_status);
 }
 
 extern "C" int rf_assoc_put_device(rf_assoc* a, int kind, const void* d_expect32, const void* d_keys32,

@@ -111,6 +111,7 @@ struct rf_ctx {
     hipStream_t stream = nullptr;
     std::mutex mu;
     DevBuf d_arena, d_out, d_tmp, d_tab, d_tab2, d_tab3, d_place;
+    DevBuf d_cw, d_cw2;  // K11's per-call scratch (device marshal, cache write; the write's Put rows): context mutex held, synced before return
     HostBuf h_stage;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     rf_sha_plan* tplan = nullptr;  // one-shot batches (transient_plan)

@@ -20,8 +20,6 @@
 
 using namespace rf;
 
-enum { kModeNone = 0, kModeBottomUp = 1, kModeTopDown = 2 };
-
 // Descent rounds enqueued between two host reads (as the plan's; RF_WAVE_BATCH
 // overrides, 0: the whole depth bound).
 static uint32_t wave_round_batch(uint32_t depth) {
@@ -32,31 +30,6 @@ static uint32_t wave_round_batch(uint32_t depth) {
     }
     return std::max<uint32_t>(b, 1);
 }
-
-struct rf_eval_wave {
-    rf_ctx* ctx = nullptr;
-    int device = 0;  // (kept: close must not touch a context that was destroyed first)
-    uint64_t n = 0, n_deps = 0, n_keys = 0;
-    uint32_t depth = 0, rounds = 0, round_batch = 1;
-    bool has_slots = false;
-    uint32_t max_slot = 0;
-    int mode = kModeNone;
-    int nce = 0;
-    uint32_t waves = 0, last_wave = 0;
-    WaveDev d;
-    DevBuf b_dep_ptr, b_deps, b_cons_ptr, b_cons, b_flags, b_key_ptr, b_key_slots, b_claim, b_root, b_fin, b_last,
-        b_state, b_pending, b_which, b_found, b_hitrow, b_rows, b_queue, b_wq, b_ctl;
-    DevBuf b_keys, b_ids, b_vals8, b_in;      // host-form keys; roots / listed nodes; set_flags' bytes; begin_states' input
-    DevBuf b_ln, b_lw, b_lv, b_lf, b_lcount;  // the host-form list's device outputs
-    StreamScratch sc_tiles;                   // the list's tile counts, handed between streams
-    uint32_t ctl[kWaveWords] = {};            // as last read
-    std::vector<DevBuf*> all() {
-        return {&b_dep_ptr, &b_deps,  &b_cons_ptr, &b_cons,  &b_flags,  &b_key_ptr, &b_key_slots, &b_claim, &b_root,
-                &b_fin,     &b_last,  &b_state,    &b_pending, &b_which, &b_found,   &b_hitrow,    &b_rows,  &b_queue,
-                &b_wq,      &b_ctl,   &b_keys,     &b_ids,   &b_vals8,  &b_in,      &b_ln,        &b_lw,    &b_lv,
-                &b_lf,      &b_lcount};
-    }
-};
 
 extern "C" int rf_eval_wave_consumers(uint64_t n, const uint64_t* dep_ptr, const uint32_t* deps, uint64_t* cons_ptr,
                                       uint32_t* cons) {

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "cwrite_internal.h"
 #include "engine.h"
 #include "host_par.h"
 #include "live_internal.h"
@@ -228,6 +229,15 @@ extern "C" int rf_repo_put_device(rf_repo* r, const void* d_ids32, const void* d
     if (int rc = repo_quiesce(r)) return rc;
     return repo_put_locked(r, static_cast<const uint8_t*>(d_ids32), static_cast<const int64_t*>(d_sizes), n,
                            static_cast<int32_t*>(d_status), pick(ctx, stream));
+}
+
+rf_ctx* rf::repo_ctx(rf_repo* r) { return r->ctx; }
+int rf::repo_put_rows_locked(rf_repo* r, const uint8_t* d_ids, const int64_t* d_sizes, uint64_t n, int32_t* d_status,
+                             hipStream_t s) {
+    char msg[160];
+    if (!repo_rows_check(n, msg, sizeof msg)) return fail(RF_EINVAL, "repo put: %s", msg);
+    if (int rc = repo_quiesce(r)) return rc;
+    return repo_put_locked(r, d_ids, d_sizes, n, d_status, s);
 }
 
 static int repo_remove_locked(rf_repo* r, const uint8_t* d_ids, uint64_t n, uint8_t* d_removed, hipStream_t s) {

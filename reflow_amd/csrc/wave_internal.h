@@ -7,6 +7,8 @@
 #include "ctx.h"
 #include "engine.h"
 
+#include <vector>
+
 namespace rf {
 
 // control words (u32) of a wave object, device memory
@@ -63,6 +65,38 @@ struct WaveLook {
     AssocView t{};
     uint32_t kind = 0;
 };
+
+// the object behind rf_eval_wave* (eval_wave.cpp; cache_write.cpp reads its structure and states)
+enum { kModeNone = 0, kModeBottomUp = 1, kModeTopDown = 2 };
+
+}  // namespace rf
+
+struct rf_eval_wave {
+    rf_ctx* ctx = nullptr;
+    int device = 0;  // (kept: close must not touch a context that was destroyed first)
+    uint64_t n = 0, n_deps = 0, n_keys = 0;
+    uint32_t depth = 0, rounds = 0, round_batch = 1;
+    bool has_slots = false;
+    uint32_t max_slot = 0;
+    int mode = rf::kModeNone;
+    int nce = 0;
+    uint32_t waves = 0, last_wave = 0;
+    rf::WaveDev d;
+    DevBuf b_dep_ptr, b_deps, b_cons_ptr, b_cons, b_flags, b_key_ptr, b_key_slots, b_claim, b_root, b_fin, b_last,
+        b_state, b_pending, b_which, b_found, b_hitrow, b_rows, b_queue, b_wq, b_ctl;
+    DevBuf b_keys, b_ids, b_vals8, b_in;      // host-form keys; roots / listed nodes; set_flags' bytes; begin_states' input
+    DevBuf b_ln, b_lw, b_lv, b_lf, b_lcount;  // the host-form list's device outputs
+    StreamScratch sc_tiles;                   // the list's tile counts, handed between streams
+    uint32_t ctl[rf::kWaveWords] = {};        // as last read
+    std::vector<DevBuf*> all() {
+        return {&b_dep_ptr, &b_deps,  &b_cons_ptr, &b_cons,  &b_flags,  &b_key_ptr, &b_key_slots, &b_claim, &b_root,
+                &b_fin,     &b_last,  &b_state,    &b_pending, &b_which, &b_found,   &b_hitrow,    &b_rows,  &b_queue,
+                &b_wq,      &b_ctl,   &b_keys,     &b_ids,   &b_vals8,  &b_in,      &b_ln,        &b_lw,    &b_lv,
+                &b_lf,      &b_lcount};
+    }
+};
+
+namespace rf {
 
 // begin, bottom-up: roots claimed (advance moves the bounds), then descent rounds
 hipError_t launch_wave_seed(const WaveDev& w, const uint32_t* roots, uint32_t n_roots, hipStream_t s);
