@@ -47,7 +47,9 @@ typedef enum {
     RF_EDEVICE = 4,    /* errors.Unavailable: HIP runtime / device failure   */
     RF_ENOMEM = 5,     /* errors.ResourcesExhausted: HBM or host allocation  */
     RF_ENOTFOUND = 6,  /* errors.NotExist                                     */
-    RF_EPRECONDITION = 7 /* errors.Precondition: assoc compare-and-set failed */
+    RF_EPRECONDITION = 7, /* errors.Precondition: assoc compare-and-set failed */
+    RF_ENOTCANONICAL = 8  /* per-document status of the Fileset unmarshal, never a call's return: not the
+                             encoder's bytes, decode it on the Go path (no errors.Kind: not an error) */
 } rf_status;
 
 typedef struct rf_ctx rf_ctx;
@@ -389,6 +391,113 @@ void rf_json_batch_free(rf_json_batch *b);
  * (i64, may be NULL) = its JSON length. */
 int rf_fileset_value_digest_device(rf_ctx *ctx, const rf_fileset_tree *t, const uint32_t *roots, uint64_t n,
                                    const void *d_ids32, void *d_out32, void *d_sizes, void *stream);
+
+/* ---- Fileset values unmarshalled on the device (Eval.lookup's unmarshal(fsid),
+ * eval.go:1212 -> eval.go:1971-1978 = Repository.Get + JSON decode) -----------
+ * The inverse of rf_fileset_marshal_device: a batch of JSON documents, in a
+ * device arena (the one rf_json_batch_device hands out, say) or in host bytes,
+ * becomes the flat (ID, Size) rows rf_repo_missing_device and
+ * rf_liveset_set_values_device take -- one group per document -- plus the full
+ * structure (nodes, decoded paths, IDs, sizes) for the caller's Fileset
+ * objects.
+ *
+ * Accepted is the CANONICAL form and nothing else: exactly the bytes
+ * json.Marshal(Fileset) / rf_fileset_marshal_json write.
+ *   node  := '{' [ '"List":[' node (',' node)* ']' ] [ ',' if both ]
+ *                [ '"Fileset":{' entry (',' entry)* '}' ] '}'
+ *   entry := string ':{"ID":"sha256:' 64x[0-9a-f] '","Size":' int '}'
+ *   int   := '-'? ( '0' | [1-9][0-9]* ), within int64, "-0" refused
+ * Deliberately NOT accepted, although Go's tolerant decoder takes them:
+ * whitespace, keys in another case or order, unknown or duplicate fields,
+ * "Fileset":{} and "List":[] (omitempty never emits them), and escapes the
+ * encoder never emits (a u-escape of a plain letter, \/, \b, upper-case hex).
+ * A string's units are raw bytes that need no escape (valid UTF-8 other than
+ * U+2028/U+2029), \" \\ \n \r \t, the lower-case u-escape 00XX of a control
+ * byte or of < > &, and the u-escapes fffd, 2028, 2029; they decode as Go's
+ * decoder decodes them.  Within a Map the decoded paths ascend strictly
+ * bytewise (the encoder sorts; strict order excludes duplicates).  One
+ * consequence: a document made from paths with invalid UTF-8, whose
+ * replacement bytes break that order, is reported as not canonical.  An
+ * all-zero ID, nodes nested deeper than 4096 and an empty document are refused
+ * as the marshal refuses them.  Every other document gets status
+ * RF_ENOTCANONICAL and a reason mask, contributes no node, entry or row (its
+ * group is empty; the accepted documents' outputs stay dense), and goes to the
+ * caller's Go decoder: not a silent fallback, the status says which.  The
+ * reason names the first thing wrong reading left to right (LENGTH: the
+ * document ends where more must follow); equal bytes give an equal mask.
+ *
+ * Nodes are numbered per document in CLOSING order (post-order; the root is a
+ * document's last node) with their depth (root 0): the entries stand in
+ * document order, and the entries between two closing braces are the later
+ * node's Map, so entry_ptr is one CSR over nodes and entries.  Closing order
+ * with depths determines the tree; rf_fileset_forest_tree rebuilds the List
+ * CSR of rf_fileset_tree from it in O(nodes) on the host.
+ *
+ * The device form works in tiles of RF_UNMARSHAL_TILE arena bytes, every pass
+ * tile summary / scan of summaries / apply, no atomic on a shared counter:
+ * quote bits, in-string parity, token checks and counts, nesting depth, then
+ * the scatter; the results are a function of the bytes alone.  Documents may
+ * start at any byte offset; they must be ascending, non-overlapping and inside
+ * the arena (RF_EINVAL otherwise, found on the device and reported after the
+ * call's one read-back).  An arena of 4 GiB or more is RF_EINVAL.  d_arena
+ * must be 16-byte aligned. */
+#define RF_UNMARSHAL_TILE 4096 /* arena bytes per tile of the unmarshal's passes */
+#define RF_UNMARSHAL_WHY_STRUCTURE 1u
+#define RF_UNMARSHAL_WHY_STRING 2u
+#define RF_UNMARSHAL_WHY_ID 4u
+#define RF_UNMARSHAL_WHY_SIZE 8u
+#define RF_UNMARSHAL_WHY_ORDER 16u
+#define RF_UNMARSHAL_WHY_DEPTH 32u
+#define RF_UNMARSHAL_WHY_LENGTH 64u
+#define RF_UNMARSHAL_CHECK_TILED 1u /* rf_fileset_unmarshal_flat: also run the kernels' per-byte form on the host */
+typedef struct rf_fileset_forest rf_fileset_forest;
+/* Host only, no context, not a product path: document d = json[offs[d],
+ * offs[d + 1]), parsed on `threads` host threads (0: up to 16) by the
+ * sequential form of the code the kernels run.  With RF_UNMARSHAL_CHECK_TILED
+ * every document also goes through the per-byte form of the kernels, and a
+ * differing verdict or count fails the call with RF_EDEVICE. */
+int rf_fileset_unmarshal_flat(const uint8_t *json, const uint64_t *offs /* n + 1 */, uint64_t n, uint32_t flags,
+                              unsigned threads, rf_fileset_forest **out);
+/* Document d = d_arena[d_offs[d], d_offs[d] + d_lens[d]) (u64 / i64 device
+ * arrays, as rf_json_batch_device gives them).  Returns when the results are
+ * complete.  n = 0 gives an empty forest. */
+int rf_fileset_unmarshal_device(rf_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const void *d_offs,
+                                const void *d_lens, uint64_t n, rf_fileset_forest **out, void *stream);
+/* The same over packed host bytes (document d = json[offs[d], offs[d + 1])),
+ * which the call uploads. */
+int rf_fileset_unmarshal(rf_ctx *ctx, const uint8_t *json, const uint64_t *offs /* n + 1 */, uint64_t n,
+                         rf_fileset_forest **out, void *stream);
+/* Documents, accepted documents, nodes, entries, decoded path bytes; any pointer may be NULL. */
+int rf_fileset_forest_info(const rf_fileset_forest *f, uint64_t *n_docs, uint64_t *n_accepted, uint64_t *n_nodes,
+                           uint64_t *n_entries, uint64_t *path_bytes);
+/* Per document: RF_OK / RF_ENOTCANONICAL, the reason mask, nodes and entries (0
+ * for a refused one).  entry_counts is the `counts` argument of
+ * rf_liveset_set_values[_device].  Any pointer may be NULL. */
+int rf_fileset_forest_status(const rf_fileset_forest *f, int32_t *status, uint32_t *reason, uint32_t *node_counts,
+                             uint32_t *entry_counts);
+/* The value rows in HBM, valid until rf_fileset_forest_free: d_counts (u32 per
+ * document), d_ids32 (32 B rows, 16-byte aligned), d_sizes (i64) and their
+ * number -- the arguments of rf_repo_missing_device.  RF_EINVAL for a
+ * host-form forest. */
+int rf_fileset_forest_rows_device(const rf_fileset_forest *f, const void **d_counts, const void **d_ids32,
+                                  const void **d_sizes, uint64_t *n_rows);
+/* The structure on the host; any pointer may be NULL.  doc_node_ptr [docs + 1],
+ * node_depth [nodes], entry_ptr [nodes + 1], path_off [entries + 1], paths
+ * [path bytes] decoded, ids32 [entries][32], sizes [entries]. */
+int rf_fileset_forest_copy(rf_fileset_forest *f, uint64_t *doc_node_ptr, uint32_t *node_depth, uint64_t *entry_ptr,
+                           uint64_t *path_off, uint8_t *paths, uint8_t *ids32, int64_t *sizes);
+/* Host only: the List CSR of rf_fileset_tree over the forest's node numbering
+ * (entry_ptr of the copy is the tree's entry_ptr as it stands) and one root per
+ * document, 0xffffffff for a refused one.  list_child has room for n_nodes. */
+int rf_fileset_forest_tree(const uint64_t *doc_node_ptr, uint64_t n_docs, const uint32_t *node_depth,
+                           uint64_t n_nodes, uint64_t *list_ptr /* n_nodes + 1 */, uint32_t *list_child,
+                           uint32_t *roots /* n_docs */);
+/* Host clock, milliseconds: ms[0] the upload of the host-input form (0 in the
+ * device form), ms[1] the check passes and scans up to and including the
+ * read-back, ms[2] the outputs' allocation + the scatter (each ends in a
+ * synchronise). */
+int rf_fileset_forest_times(const rf_fileset_forest *f, double ms[3]);
+void rf_fileset_forest_free(rf_fileset_forest *f);
 
 /* ---- Coalescing concurrent callers (SURVEY §8(b) "Threading") -----------
  * The reference digests files in <=60 goroutines (local/executor.go:41,

@@ -253,6 +253,11 @@ std::vector<Digest> FilesetDigests(Engine& e, const std::vector<const Fileset*>&
 // CacheWrite stores under each cache key (SHA-256 on the GPU).
 std::string MarshalJSON(const Fileset& v);
 std::vector<Digest> FilesetValueDigests(Engine& e, const std::vector<const Fileset*>& v);
+// Eval.lookup's unmarshal (eval.go:1212, 1971-1978) for a batch of values read
+// from the repository, parsed on the GPU (rf_fileset_unmarshal).  Only the
+// canonical bytes json.Marshal writes are accepted (reflow_hip.h has the
+// rule): an empty optional is a document to decode with the tolerant decoder.
+std::vector<std::optional<Fileset>> UnmarshalFilesets(Engine& e, const std::vector<std::string>& docs);
 // Executor.install (local/executor.go:514-557): walk `path` like
 // internal/walker (symlinks followed, missing paths skipped, sorted
 // depth-first), digest every file on the GPU -> Fileset{Map: relpath -> File}.

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreflow_hip.so")
 
 RF_OK, RF_EINVAL, RF_EIO, RF_EINTEGRITY, RF_EDEVICE, RF_ENOMEM, RF_ENOTFOUND, RF_EPRECONDITION = range(8)
+RF_ENOTCANONICAL = 8  # per-document status of the Fileset unmarshal
 RF_SHA_NO_SOLO = 1
 RF_SHA_ALL_SOLO = 2
 RF_SHA_ONE_LANE_CHAIN = 4
@@ -47,6 +48,11 @@ RF_REPO_MIN_SLOTS = 1024
 RF_REPO_LIST_TILE = 1024
 # device marshal of Fileset values (rf_fileset_marshal_device): pieces per tile
 RF_MARSHAL_TILE = 1024
+# device unmarshal of Fileset values (rf_fileset_unmarshal_device): arena bytes per tile, reason bits, flat-form flag
+RF_UNMARSHAL_TILE = 4096
+(RF_UNMARSHAL_WHY_STRUCTURE, RF_UNMARSHAL_WHY_STRING, RF_UNMARSHAL_WHY_ID, RF_UNMARSHAL_WHY_SIZE,
+ RF_UNMARSHAL_WHY_ORDER, RF_UNMARSHAL_WHY_DEPTH, RF_UNMARSHAL_WHY_LENGTH) = 1, 2, 4, 8, 16, 32, 64
+RF_UNMARSHAL_CHECK_TILED = 1
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -102,6 +108,9 @@ EXPORTS = [
     "rf_fileset_marshal_flat", "rf_fileset_marshal_device", "rf_json_batch_info", "rf_json_batch_times", "rf_json_batch_lens",
     "rf_json_batch_device", "rf_json_batch_copy", "rf_json_batch_digests_device", "rf_json_batch_free",
     "rf_fileset_value_digest_device", "rf_eval_wave_cache_write",
+    "rf_fileset_unmarshal_flat", "rf_fileset_unmarshal_device", "rf_fileset_unmarshal", "rf_fileset_forest_info",
+    "rf_fileset_forest_status", "rf_fileset_forest_rows_device", "rf_fileset_forest_copy", "rf_fileset_forest_tree",
+    "rf_fileset_forest_times", "rf_fileset_forest_free",
 ]
 
 
@@ -220,6 +229,159 @@ def fileset_marshal_flat(sets):
                                          _ptr(offs), ctypes.byref(need)))
     assert int(offs[n]) == need.value
     return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+
+class Fileset:
+    """A decoded Fileset value: .list (None or a list of Fileset) and .map (None
+    or a dict path bytes -> (id32, size), in key order) -- the shape
+    FilesetTreeBuilder and the oracle's OFileset have; omitempty's absent List
+    and Map are None."""
+
+    def __init__(self, map=None, list=None):
+        self.map, self.list = map, list
+
+    def flat(self):
+        """[(depth, ((path, id32, size), ...))] per node in closing order (post-order),
+        which determines the value; no recursion, so any depth compares."""
+        out, stack = [], [(self, 0, False)]
+        while stack:
+            v, d, seen = stack.pop()
+            if seen:
+                out.append((d, tuple((k, e[0], e[1]) for k, e in (v.map or {}).items())))
+                continue
+            stack.append((v, d, True))
+            stack.extend((c, d + 1, False) for c in reversed(v.list or ()))
+        return out
+
+    def __eq__(self, other):
+        return isinstance(other, Fileset) and self.flat() == other.flat()
+
+    def __repr__(self):
+        return "Fileset(map=%r, list=%r)" % (self.map, self.list)
+
+
+def pack_docs(docs):
+    """(uint8 array, uint64 offsets [n + 1]) of documents packed back to back."""
+    offs = np.zeros(len(docs) + 1, dtype=np.uint64)
+    if docs:
+        offs[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(docs) or b"\0", dtype=np.uint8).copy()
+    return buf, offs
+
+
+class FilesetForest:
+    """rf_fileset_forest: a batch of Fileset JSON documents unmarshalled, by the
+    host form (flat) or on the device."""
+
+    def __init__(self, handle, ctx=None):
+        self._h, self.ctx = handle, ctx
+        v = [ctypes.c_uint64() for _ in range(5)]
+        _check(lib().rf_fileset_forest_info(self._h, *[ctypes.byref(x) for x in v]))
+        self.n_docs, self.n_accepted, self.n_nodes, self.n_entries, self.path_bytes = [x.value for x in v]
+
+    @classmethod
+    def flat(cls, docs, flags=RF_UNMARSHAL_CHECK_TILED, threads=0):
+        buf, offs = pack_docs(docs)
+        h = ctypes.c_void_p()
+        _check(lib().rf_fileset_unmarshal_flat(_ptr(buf), _ptr(offs), len(docs), flags, threads, ctypes.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_host(cls, ctx, docs, stream=None):
+        buf, offs = pack_docs(docs)
+        h = ctypes.c_void_p()
+        _check(lib().rf_fileset_unmarshal(ctx.handle, _ptr(buf), _ptr(offs), len(docs), ctypes.byref(h), stream))
+        return cls(h, ctx)
+
+    @classmethod
+    def from_device(cls, ctx, d_arena, arena_bytes, d_offs, d_lens, n, stream=None):
+        h = ctypes.c_void_p()
+        _check(lib().rf_fileset_unmarshal_device(ctx.handle, d_arena, arena_bytes, d_offs, d_lens, n, ctypes.byref(h),
+                                                 stream))
+        return cls(h, ctx)
+
+    def status(self):
+        """(status i32, reason u32, node counts u32, entry counts u32), one per document."""
+        n = self.n_docs
+        a = [np.zeros(max(n, 1), dtype=t) for t in (np.int32, np.uint32, np.uint32, np.uint32)]
+        _check(lib().rf_fileset_forest_status(self._h, *[_ptr(x) for x in a]))
+        return tuple(x[:n] for x in a)
+
+    def rows_device(self):
+        """(d_counts, d_ids32, d_sizes, n_rows): rf_repo_missing_device's arguments."""
+        c, i, s, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().rf_fileset_forest_rows_device(self._h, ctypes.byref(c), ctypes.byref(i), ctypes.byref(s),
+                                                   ctypes.byref(n)))
+        return c.value, i.value, s.value, n.value
+
+    def copy(self):
+        """The structure on the host: a dict of doc_node_ptr, node_depth, entry_ptr,
+        path_off, paths, ids32, sizes (numpy arrays)."""
+        o = dict(doc_node_ptr=np.zeros(self.n_docs + 1, np.uint64), node_depth=np.zeros(max(self.n_nodes, 1), np.uint32),
+                 entry_ptr=np.zeros(self.n_nodes + 1, np.uint64), path_off=np.zeros(self.n_entries + 1, np.uint64),
+                 paths=np.zeros(max(self.path_bytes, 1), np.uint8), ids32=np.zeros(max(32 * self.n_entries, 1), np.uint8),
+                 sizes=np.zeros(max(self.n_entries, 1), np.int64))
+        _check(lib().rf_fileset_forest_copy(self._h, *[_ptr(o[k]) for k in (
+            "doc_node_ptr", "node_depth", "entry_ptr", "path_off", "paths", "ids32", "sizes")]))
+        o["node_depth"] = o["node_depth"][:self.n_nodes]
+        o["paths"] = o["paths"][:self.path_bytes]
+        o["ids32"] = o["ids32"][:32 * self.n_entries]
+        o["sizes"] = o["sizes"][:self.n_entries]
+        return o
+
+    def times(self):
+        ms = (ctypes.c_double * 3)()
+        _check(lib().rf_fileset_forest_times(self._h, ms))
+        return tuple(ms)
+
+    def values(self, structure=None):
+        """One Fileset per document, None for a refused one (through
+        rf_fileset_forest_tree)."""
+        o = structure or self.copy()
+        nn, nd = self.n_nodes, self.n_docs
+        lp, lc = np.zeros(nn + 1, np.uint64), np.zeros(max(nn, 1), np.uint32)
+        roots = np.zeros(max(nd, 1), np.uint32)
+        _check(lib().rf_fileset_forest_tree(_ptr(o["doc_node_ptr"]), nd, _ptr(o["node_depth"]) if nn else None, nn,
+                                            _ptr(lp), _ptr(lc), _ptr(roots)))
+        paths, po, ids, sizes, ep = o["paths"].tobytes(), o["path_off"], o["ids32"].tobytes(), o["sizes"], o["entry_ptr"]
+        made = [None] * nn
+        for p in range(nn):  # closing order: a node's List is made before it
+            kids = [made[c] for c in lc[int(lp[p]):int(lp[p + 1])]]
+            m = {paths[int(po[e]):int(po[e + 1])]: (ids[32 * e:32 * e + 32], int(sizes[e]))
+                 for e in range(int(ep[p]), int(ep[p + 1]))}
+            made[p] = Fileset(map=m or None, list=kids or None)
+        return [None if roots[d] == 0xffffffff else made[int(roots[d])] for d in range(nd)]
+
+    def close(self):
+        if self._h:
+            lib().rf_fileset_forest_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fileset_unmarshal_flat(docs, flags=RF_UNMARSHAL_CHECK_TILED):
+    """Each document through the host form (and, by default, the kernels'
+    per-byte form beside it): a list of Fileset, None where refused."""
+    f = FilesetForest.flat(docs, flags)
+    try:
+        return f.values()
+    finally:
+        f.close()
+
+
+def fileset_unmarshal(ctx, docs=None, device=None):
+    """The device form over host documents, or over device=(d_arena, arena_bytes,
+    d_offs, d_lens, n): a list of Fileset, None where refused."""
+    f = FilesetForest.from_host(ctx, docs) if device is None else FilesetForest.from_device(ctx, *device)
+    try:
+        return f.values()
+    finally:
+        f.close()
 
 
 class JsonBatch:
@@ -650,6 +812,15 @@ def lib():
             "rf_json_batch_digests_device": ([vp, vp, vp], i32), "rf_json_batch_free": ([vp], None),
             "rf_fileset_value_digest_device": ([vp, vp, vp, u64, vp, vp, vp, vp], i32),
             "rf_eval_wave_cache_write": ([vp, vp, u64, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp], i32),
+            "rf_fileset_unmarshal_flat": ([vp, vp, u64, u32, u32, vp], i32),
+            "rf_fileset_unmarshal_device": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
+            "rf_fileset_unmarshal": ([vp, vp, vp, u64, vp, vp], i32),
+            "rf_fileset_forest_info": ([vp, vp, vp, vp, vp, vp], i32),
+            "rf_fileset_forest_status": ([vp, vp, vp, vp, vp], i32),
+            "rf_fileset_forest_rows_device": ([vp, vp, vp, vp, vp], i32),
+            "rf_fileset_forest_copy": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
+            "rf_fileset_forest_tree": ([vp, u64, vp, u64, vp, vp, vp], i32),
+            "rf_fileset_forest_times": ([vp, vp], i32), "rf_fileset_forest_free": ([vp], None),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)

@@ -9,6 +9,9 @@ namespace rf {
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 }  // namespace rf
 
+// RF_ENOTCANONICAL (reflow_hip.h) is a per-document status of the Fileset
+// unmarshal: fail() never carries it and no call returns it.
+
 #define ARG(cond, msg)                                       \
     do {                                                     \
         if (!(cond)) return rf::fail(RF_EINVAL, "%s", msg); \

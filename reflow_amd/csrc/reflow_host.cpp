@@ -239,6 +239,53 @@ std::vector<Digest> FilesetValueDigests(Engine& e, const std::vector<const Files
     return out;
 }
 
+std::vector<std::optional<Fileset>> UnmarshalFilesets(Engine& e, const std::vector<std::string>& docs) {
+    std::string all;
+    std::vector<uint64_t> offs{0};
+    for (const std::string& d : docs) {
+        all += d;
+        offs.push_back(all.size());
+    }
+    rf_fileset_forest* f = nullptr;
+    Check(rf_fileset_unmarshal(e.ctx(), reinterpret_cast<const uint8_t*>(all.data()), offs.data(), docs.size(), &f,
+                               nullptr));
+    std::unique_ptr<rf_fileset_forest, void (*)(rf_fileset_forest*)> hold(f, rf_fileset_forest_free);
+    uint64_t nn = 0, ne = 0, pb = 0;
+    Check(rf_fileset_forest_info(f, nullptr, nullptr, &nn, &ne, &pb));
+    std::vector<uint64_t> doc_ptr(docs.size() + 1), entry_ptr(nn + 1), path_off(ne + 1);
+    std::vector<uint32_t> depth(nn + 1);
+    std::vector<uint8_t> paths(pb + 1), ids(32 * ne + 1);
+    std::vector<int64_t> sizes(ne + 1);
+    Check(rf_fileset_forest_copy(f, doc_ptr.data(), depth.data(), entry_ptr.data(), path_off.data(), paths.data(),
+                                 ids.data(), sizes.data()));
+    // nodes come in closing order: a node's List is the run of deeper nodes on top of the stack
+    std::vector<std::optional<Fileset>> out(docs.size());
+    for (size_t d = 0; d < docs.size(); ++d) {
+        std::vector<std::pair<uint32_t, Fileset>> stack;
+        for (uint64_t p = doc_ptr[d]; p < doc_ptr[d + 1]; ++p) {
+            Fileset v;
+            size_t k = stack.size();
+            while (k > 0 && stack[k - 1].first == depth[p] + 1) --k;
+            if (k < stack.size()) {
+                v.List.emplace();
+                for (size_t j = k; j < stack.size(); ++j) v.List->push_back(std::move(stack[j].second));
+                stack.resize(k);
+            }
+            for (uint64_t x = entry_ptr[p]; x < entry_ptr[p + 1]; ++x) {
+                File file;
+                memcpy(file.ID.b.data(), ids.data() + 32 * x, 32);
+                file.Size = sizes[x];
+                v.Map.emplace(std::string(reinterpret_cast<const char*>(paths.data()) + path_off[x],
+                                          path_off[x + 1] - path_off[x]),
+                              file);
+            }
+            stack.emplace_back(depth[p], std::move(v));
+        }
+        if (stack.size() == 1) out[d] = std::move(stack[0].second);
+    }
+    return out;
+}
+
 // ---- flows ----------------------------------------------------------------------
 std::string DigestString(Op op) {
     static const char* names[] = {"OpExec", "OpIntern", "OpExtern", "OpGroupby", "OpMap",
