@@ -1527,6 +1527,133 @@ int rf_eval_wave_cache_write(rf_eval_wave *w, const uint32_t *nodes, uint64_t n,
                              const void *d_keys32, rf_assoc *a, int kind, rf_repo *repo /* may be NULL */,
                              rf_cache_write_out *o /* may be NULL */, void *stream);
 
+/* ---- Physical cache keys (Flow.PhysicalDigest, flow.go:764-792) ----------------
+ * The key that moves when a consumer's deps get their values: SHA256(FM(dep 0)
+ * ‖ ... ‖ FM(dep k) ‖ suffix), computable once every dep has a value, the zero
+ * digest (a row of 32 zero bytes, rf_eval_wave_step's "absent" row) before
+ * that.  FM is Fileset.WriteDigest (executor.go:214-233): `path ‖ 00 05 ‖ ID`
+ * over the Map entries in bytewise path order, a non-empty List flattened in
+ * its place ("List wins").  An rf_physkeys object keeps each finished node's
+ * material in an HBM arena, built on the device from the arrays an unmarshal
+ * left there, and writes the keys of the affected consumers into the caller's
+ * d_keys32 rows, where rf_eval_wave_step, rf_eval_plan_run and
+ * rf_eval_wave_cache_write read them.  A bottom-up round is then: step ->
+ * unmarshal the hits -> rf_repo_missing_device -> rf_physkeys_set_values_forest
+ * -> rf_physkeys_update -> next step, with no per-file or per-node host work.
+ *
+ * Open: n, dep_ptr, deps as rf_eval_plan_open takes and checks them (a dep
+ * listed twice contributes twice).  phys_row[i] = the row of d_keys32 that holds
+ * node i's physical key, RF_PHYS_NO_ROW for a node that has none (one that is
+ * not OpExec / OpExtern); a row used twice is RF_EINVAL.  suffix[suffix_ptr[i] ..
+ * suffix_ptr[i+1]) is what follows the deps' materials: URL.String() for
+ * OpExtern, Image ‖ Cmd ‖ LE64 argmap for OpExec, rendered by the host
+ * (SURVEY Appendix B.5-6); pointers that are not monotone are RF_EINVAL.
+ *
+ * Passes, all strided fixed grids or tiles, no atomic on a shared counter, each
+ * reading what the one before wrote after the kernel boundary, the results a
+ * function of the inputs alone: per forest node a contribution flag and length
+ * (a node contributes its Map iff it has no List children, which in closing
+ * order is: it is the document's first node or the node before it is not one
+ * level deeper) and their scan in tiles of RF_PHYS_LIST_TILE; the emit of the
+ * entries into the store's arena, each value at a 16-byte aligned offset, pad
+ * bytes zero; for an update the affected set (a byte per node, every writer
+ * stores the same 1; listed ascending by tile count / scan / scatter), a
+ * computable bit and a material length per affected node, the segment table
+ * (per dep the offset and length of its material, then the suffix), the gather
+ * into a scratch arena in tiles of RF_PHYS_COPY_TILE output bytes (a tile finds
+ * the segment of its first byte by search), K1 over that arena through the
+ * one-shot plan of rf_json_batch_digests_device (GPU legs only; the lengths are
+ * read back once for its planner), and the scatter of digests and zero rows.
+ * The arena's growth is decided on the host before a launch.
+ *
+ * The store does not compact: a replaced or cleared value leaves its bytes
+ * behind as stale bytes (rf_physkeys_stats), as the liveset's rows do.
+ * Out of scope: physical jobs inside an rf_graph and keys read through
+ * key_slots (d_keys32 rows only); reusing a SHA midstate across consumers that
+ * share a leading dep; compaction; dep.Err; graphs that grow at run time;
+ * values that are not Filesets. */
+#define RF_PHYS_NO_ROW 0xffffffffffffffffull
+#define RF_PHYS_SELF 1u       /* rf_physkeys_update: the listed nodes */
+#define RF_PHYS_CONSUMERS 2u  /* every consumer of a listed node, each once */
+#define RF_PHYS_LIST_TILE 1024 /* forest nodes, graph nodes or affected nodes per tile of a scan */
+#define RF_PHYS_COPY_TILE 4096 /* output bytes per workgroup of the gather */
+typedef struct rf_physkeys rf_physkeys;
+int rf_physkeys_open(rf_ctx *ctx, uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, const uint64_t *phys_row,
+                     const uint64_t *suffix_ptr, const uint8_t *suffix, rf_physkeys **out);
+void rf_physkeys_close(rf_physkeys *pk);
+/* Document d of a device-form forest becomes the value of nodes[d] (host array,
+ * one per document); 0xffffffff skips the document.  RF_EINVAL for a refused
+ * document with a real node, a node >= n, a host-form forest.  A node listed
+ * twice keeps its last value.  A failed call changes no value.  Returns when
+ * the values are set. */
+int rf_physkeys_set_values_forest(rf_physkeys *pk, const uint32_t *nodes, const rf_fileset_forest *f, void *stream);
+/* Values that did not come from JSON (an exec's output): roots[d] of the tree
+ * becomes the value of nodes[d], the File IDs optionally in device rows (K1's
+ * output, entry e's at row e), as rf_fileset_marshal_device takes them.  The
+ * host walks the tree, orders the Maps that are not in order and uploads paths
+ * and the entry order; the same device passes then run.  Refusals are those of
+ * rf_fileset_marshal_device, a zero ID excepted: material has no such rule. */
+int rf_physkeys_set_values_tree(rf_physkeys *pk, const uint32_t *nodes, const rf_fileset_tree *t,
+                                const uint32_t *roots, uint64_t n, const void *d_ids32, void *stream);
+/* These nodes are no longer FlowDone. */
+int rf_physkeys_clear_values(rf_physkeys *pk, const uint32_t *nodes, uint64_t n);
+typedef struct {
+    uint64_t size;           /* = sizeof(rf_physkeys_out), set by the caller */
+    uint64_t affected;       /* affected nodes that have a phys_row */
+    uint64_t keys_written;   /* of them, computable: a digest written */
+    uint64_t keys_zeroed;    /* of them, not computable: a zero row written */
+    uint64_t material_bytes; /* hashed bytes, unpadded */
+    uint64_t cap;            /* room in the two arrays below (set by the caller) */
+    uint32_t *nodes;         /* host, [cap] or NULL: the affected nodes, ascending, as far as they fit */
+    uint8_t *computable;     /* host, [cap] or NULL: 1 where a digest was written */
+} rf_physkeys_out;
+/* The affected nodes (flags: RF_PHYS_SELF, RF_PHYS_CONSUMERS or both) that have
+ * a phys_row, in ascending node order: if every dep has a value,
+ * d_keys32[phys_row] becomes SHA256(the deps' materials in Deps order ‖ suffix),
+ * otherwise 32 zero bytes (a dep that is done but has no Fileset value panics in
+ * the reference, flow.go:775; here it is "no value").  Rows of other nodes are
+ * not touched.  A phys_row >= n_rows is RF_EINVAL with nothing written, and so
+ * is a call whose padded materials would reach 4 GiB (split it).  d_keys32 is
+ * 16-byte aligned.  Holds the context's lock; returns when the rows are written. */
+int rf_physkeys_update(rf_physkeys *pk, const uint32_t *nodes, uint64_t n, uint32_t flags, void *d_keys32,
+                       uint64_t n_rows, rf_physkeys_out *o /* may be NULL */, void *stream);
+/* d_out32[i] = Fileset.Digest() = SHA256(material) of nodes[i]'s value, straight
+ * from the stored material (Fileset.Equal, OpVal's logical digest); a node
+ * without a value is RF_EINVAL. */
+int rf_physkeys_value_digests_device(rf_physkeys *pk, const uint32_t *nodes, uint64_t n, void *d_out32, void *stream);
+/* Host read-back of one value's material, for tests: *len is set either way,
+ * RF_EINVAL when cap is short or the node has no value. */
+int rf_physkeys_value_material(rf_physkeys *pk, uint32_t node, uint8_t *out, uint64_t cap, uint64_t *len);
+typedef struct {
+    uint64_t n_nodes, n_values; /* graph nodes; of them, with a value */
+    uint64_t arena_bytes;       /* used bytes of the store's arena, pads included */
+    uint64_t stale_bytes;       /* of them, belonging to replaced or cleared values */
+    uint64_t device_bytes;      /* everything the object holds in HBM */
+    double last_ms[6];          /* the last update: affected set / lengths + read-back / segments / gather / K1 / scatter */
+} rf_physkeys_stats;
+int rf_physkeys_stats_get(rf_physkeys *pk, rf_physkeys_stats *out);
+/* Host only, no context, not a product path: the same open arguments, the values
+ * (value d belongs to nodes[d]) as the host arrays of rf_fileset_forest_copy or
+ * as tree + roots (exactly one of fa and tree), run through the per-entry and
+ * per-segment code the kernels run (SHA-256 on the host).  Every node with a
+ * phys_row gets its row of keys32 [n_rows][32]: the key, or zero bytes.  Value
+ * d's material lands at materials + mat_offs[d] (packed; mat_offs may be NULL),
+ * mat_offs[n_values] = *out_len = the bytes needed, set either way; RF_EINVAL
+ * with nothing written when cap is short. */
+typedef struct {
+    uint64_t n_docs;
+    const uint64_t *doc_node_ptr; /* [n_docs + 1] */
+    const uint32_t *node_depth;
+    const uint64_t *entry_ptr;
+    const uint64_t *path_off;
+    const uint8_t *paths;
+    const uint8_t *ids32;
+} rf_forest_arrays;
+int rf_physkeys_flat(uint64_t n, const uint64_t *dep_ptr, const uint32_t *deps, const uint64_t *phys_row,
+                     const uint64_t *suffix_ptr, const uint8_t *suffix, const uint32_t *nodes, uint64_t n_values,
+                     const rf_forest_arrays *fa, const rf_fileset_tree *tree, const uint32_t *roots, uint8_t *keys32,
+                     uint64_t n_rows, uint8_t *materials, uint64_t cap, uint64_t *mat_offs, uint64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -818,4 +818,45 @@ class RepoIndex {
     rf_repo* r_ = nullptr;
 };
 
+// Flow.PhysicalDigest (flow.go:764-792) for a whole Flow graph, on the device
+// (rf_physkeys_*): the finished nodes' Fileset materials are kept in HBM, and
+// the keys of the consumers they affect are written into the caller's key rows
+// -- the rows EvalPlan / EvalWave read.  Nodes are numbered by the caller as for
+// EvalWave; phys_row[i] is node i's row or NoRow (a node that is not OpExec /
+// OpExtern); suffixes[i] is what follows the deps' materials: URL.String() for
+// an OpExtern, Image ‖ Cmd ‖ LE64 argmap for an OpExec.
+class PhysicalKeys {
+   public:
+    static constexpr uint64_t NoRow = RF_PHYS_NO_ROW;
+    PhysicalKeys(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+                 const std::vector<uint64_t>& phys_row, const std::vector<std::string>& suffixes);
+    ~PhysicalKeys();
+    PhysicalKeys(const PhysicalKeys&) = delete;
+    PhysicalKeys& operator=(const PhysicalKeys&) = delete;
+    // Document d of a device-form forest (rf_fileset_unmarshal[_device]) is the
+    // value of nodes[d]; 0xffffffff skips it.  An older value is replaced.
+    void SetValues(const std::vector<uint32_t>& nodes, const rf_fileset_forest* forest);
+    // Values that did not come from JSON.  (A List that is non-nil but empty
+    // counts as nil here, as it does after a JSON round trip.)
+    void SetValues(const std::vector<uint32_t>& nodes, const std::vector<const Fileset*>& vals);
+    void ClearValues(const std::vector<uint32_t>& nodes);  // no longer FlowDone
+    struct Result {
+        uint64_t affected = 0, written = 0, zeroed = 0, material_bytes = 0;
+        std::vector<uint32_t> nodes;      // the affected nodes that have a row, ascending
+        std::vector<uint8_t> computable;  // 1: a digest was written, 0: the zero digest
+    };
+    // flags: RF_PHYS_SELF, RF_PHYS_CONSUMERS or both.  d_keys32: device rows.
+    Result Update(const std::vector<uint32_t>& nodes, uint32_t flags, void* d_keys32, uint64_t n_rows);
+    // The same over host rows (uploaded, updated, downloaded): for tests and small graphs.
+    Result Update(const std::vector<uint32_t>& nodes, uint32_t flags, std::vector<Digest>& keys);
+    std::vector<Digest> ValueDigests(const std::vector<uint32_t>& nodes);  // Fileset.Digest() of the stored values
+    std::string ValueMaterial(uint32_t node);
+    rf_physkeys_stats Stats();
+
+   private:
+    Engine& e_;
+    rf_physkeys* pk_ = nullptr;
+    uint64_t n_ = 0;
+};
+
 }  // namespace reflow

@@ -53,6 +53,12 @@ RF_UNMARSHAL_TILE = 4096
 (RF_UNMARSHAL_WHY_STRUCTURE, RF_UNMARSHAL_WHY_STRING, RF_UNMARSHAL_WHY_ID, RF_UNMARSHAL_WHY_SIZE,
  RF_UNMARSHAL_WHY_ORDER, RF_UNMARSHAL_WHY_DEPTH, RF_UNMARSHAL_WHY_LENGTH) = 1, 2, 4, 8, 16, 32, 64
 RF_UNMARSHAL_CHECK_TILED = 1
+# physical keys (rf_physkeys_*): a node without a key row, update flags, items per scan tile, bytes per gather tile
+RF_PHYS_NO_ROW = 2**64 - 1
+RF_PHYS_SELF, RF_PHYS_CONSUMERS = 1, 2
+RF_PHYS_LIST_TILE = 1024
+RF_PHYS_COPY_TILE = 4096
+RF_PHYS_SKIP = 0xffffffff  # set values: a document without a node
 
 # Every symbol include/reflow_hip.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -111,6 +117,9 @@ EXPORTS = [
     "rf_fileset_unmarshal_flat", "rf_fileset_unmarshal_device", "rf_fileset_unmarshal", "rf_fileset_forest_info",
     "rf_fileset_forest_status", "rf_fileset_forest_rows_device", "rf_fileset_forest_copy", "rf_fileset_forest_tree",
     "rf_fileset_forest_times", "rf_fileset_forest_free",
+    "rf_physkeys_open", "rf_physkeys_close", "rf_physkeys_set_values_forest", "rf_physkeys_set_values_tree",
+    "rf_physkeys_clear_values", "rf_physkeys_update", "rf_physkeys_value_digests_device",
+    "rf_physkeys_value_material", "rf_physkeys_stats_get", "rf_physkeys_flat",
 ]
 
 
@@ -607,6 +616,25 @@ class RepoMissingOut(ctypes.Structure):
                 ("n_listed", ctypes.c_void_p)]
 
 
+class PhysKeysOut(ctypes.Structure):
+    """rf_physkeys_out: what one rf_physkeys_update call did."""
+    _fields_ = [("size", ctypes.c_uint64), ("affected", ctypes.c_uint64), ("keys_written", ctypes.c_uint64),
+                ("keys_zeroed", ctypes.c_uint64), ("material_bytes", ctypes.c_uint64), ("cap", ctypes.c_uint64),
+                ("nodes", ctypes.c_void_p), ("computable", ctypes.c_void_p)]
+
+
+class PhysKeysStats(ctypes.Structure):
+    _fields_ = [("n_nodes", ctypes.c_uint64), ("n_values", ctypes.c_uint64), ("arena_bytes", ctypes.c_uint64),
+                ("stale_bytes", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("last_ms", ctypes.c_double * 6)]
+
+
+class ForestArrays(ctypes.Structure):
+    """rf_forest_arrays: the host arrays of rf_fileset_forest_copy, for rf_physkeys_flat."""
+    _fields_ = [("n_docs", ctypes.c_uint64), ("doc_node_ptr", ctypes.c_void_p), ("node_depth", ctypes.c_void_p),
+                ("entry_ptr", ctypes.c_void_p), ("path_off", ctypes.c_void_p), ("paths", ctypes.c_void_p),
+                ("ids32", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -821,6 +849,15 @@ def lib():
             "rf_fileset_forest_copy": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
             "rf_fileset_forest_tree": ([vp, u64, vp, u64, vp, vp, vp], i32),
             "rf_fileset_forest_times": ([vp, vp], i32), "rf_fileset_forest_free": ([vp], None),
+            "rf_physkeys_open": ([vp, u64, vp, vp, vp, vp, vp, vp], i32), "rf_physkeys_close": ([vp], None),
+            "rf_physkeys_set_values_forest": ([vp, vp, vp, vp], i32),
+            "rf_physkeys_set_values_tree": ([vp, vp, vp, vp, u64, vp, vp], i32),
+            "rf_physkeys_clear_values": ([vp, vp, u64], i32),
+            "rf_physkeys_update": ([vp, vp, u64, u32, vp, u64, vp, vp], i32),
+            "rf_physkeys_value_digests_device": ([vp, vp, u64, vp, vp], i32),
+            "rf_physkeys_value_material": ([vp, u32, vp, u64, vp], i32),
+            "rf_physkeys_stats_get": ([vp, vp], i32),
+            "rf_physkeys_flat": ([u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp], i32),
         }
         for name, (args, res) in sigs.items():
             f = getattr(L, name)
@@ -2424,3 +2461,157 @@ def repo_file_parse(buf: bytes, cap_entries=None):
         err.needed = n.value
         raise err
     return ids[:n.value], sizes[:n.value]
+
+
+def _phys_graph_args(dep_ptr, deps, phys_row, suffixes):
+    """The open arguments as arrays: suffixes is one bytes object per node."""
+    dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+    de = np.ascontiguousarray(deps, dtype=np.uint32)
+    pr = np.ascontiguousarray(phys_row, dtype=np.uint64)
+    n = len(pr)
+    sp = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        sp[1:] = np.cumsum([len(x) for x in suffixes], dtype=np.uint64)
+    sb = np.frombuffer(b"".join(suffixes) or b"\0", dtype=np.uint8).copy()
+    return n, dp, de, pr, sp, sb
+
+
+class PhysKeys:
+    """rf_physkeys: the finished nodes' Fileset materials in HBM and the
+    physical keys (Flow.PhysicalDigest) of the consumers they affect, written
+    into the caller's d_keys32 rows.  phys_row[i] = node i's key row or
+    RF_PHYS_NO_ROW; suffixes[i] = the bytes after the deps' materials."""
+
+    def __init__(self, ctx: Context, dep_ptr, deps, phys_row, suffixes=None, suffix_ptr=None, suffix=None):
+        self.ctx = ctx
+        if suffixes is not None:
+            self.n, dp, de, pr, sp, sb = _phys_graph_args(dep_ptr, deps, phys_row, suffixes)
+        else:  # raw arrays, as the C call takes them
+            dp = np.ascontiguousarray(dep_ptr, dtype=np.uint64)
+            de = np.ascontiguousarray(deps, dtype=np.uint32)
+            pr = np.ascontiguousarray(phys_row, dtype=np.uint64)
+            sp = np.ascontiguousarray(suffix_ptr, dtype=np.uint64)
+            sb = np.ascontiguousarray(suffix if suffix is not None and len(suffix) else np.zeros(1, np.uint8),
+                                      dtype=np.uint8)
+            self.n = len(pr)
+        self._h = ctypes.c_void_p()
+        _check(lib().rf_physkeys_open(ctx.handle, self.n, _ptr(dp) if self.n else None, _ptr(de) if len(de) else None,
+                                      _ptr(pr) if self.n else None, _ptr(sp) if self.n else None, _ptr(sb),
+                                      ctypes.byref(self._h)))
+
+    def set_values_forest(self, nodes, forest, stream=None):
+        """Document d of a device-form FilesetForest becomes the value of nodes[d] (RF_PHYS_SKIP: none)."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        assert len(nd) == forest.n_docs
+        _check(lib().rf_physkeys_set_values_forest(self._h, _ptr(nd) if len(nd) else None, forest._h, stream))
+
+    def set_values(self, nodes, sets=None, tree=None, roots=None, d_ids32=None, stream=None):
+        """Fileset objects (or tree + roots) become the values of nodes; d_ids32: the File IDs as device rows."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        if sets is not None:
+            b = FilesetTreeBuilder()
+            roots = [b.add(fs) for fs in sets]
+            tree = b.struct()
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        assert len(r) == len(nd)
+        _check(lib().rf_physkeys_set_values_tree(self._h, _ptr(nd) if len(nd) else None, ctypes.byref(tree),
+                                                 _ptr(r) if len(r) else None, len(r), d_ids32, stream))
+
+    def clear_values(self, nodes):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        _check(lib().rf_physkeys_clear_values(self._h, _ptr(nd) if len(nd) else None, len(nd)))
+
+    def update(self, nodes, flags, d_keys32, n_rows, listed=False, stream=None):
+        """rf_physkeys_update; returns the PhysKeysOut, with .affected_nodes and
+        .computable_bits (numpy) when listed."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        o = PhysKeysOut()
+        o.size = ctypes.sizeof(PhysKeysOut)
+        if listed:
+            an, cb = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint8)
+            o.cap, o.nodes, o.computable = self.n, _ptr(an), _ptr(cb)
+        _check(lib().rf_physkeys_update(self._h, _ptr(nd) if len(nd) else None, len(nd), flags, d_keys32, n_rows,
+                                        ctypes.byref(o), stream))
+        if listed:
+            o.affected_nodes, o.computable_bits = an[:o.affected], cb[:o.affected]
+        return o
+
+    def value_digests_device(self, nodes, d_out32, stream=None):
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        _check(lib().rf_physkeys_value_digests_device(self._h, _ptr(nd) if len(nd) else None, len(nd), d_out32, stream))
+
+    def value_digests(self, nodes) -> list:
+        """Fileset.Digest() of the nodes' values on the host (a device buffer and a download; for tests)."""
+        n = len(nodes)
+        if not n:
+            return []
+        d = self.ctx.alloc(32 * n)
+        try:
+            self.value_digests_device(nodes, d.ptr)
+            out = d.to_numpy(np.uint8, 32 * n)
+        finally:
+            d.free()
+        return [out[32 * i:32 * i + 32].tobytes() for i in range(n)]
+
+    def value_material(self, node) -> bytes:
+        ln = ctypes.c_uint64()
+        rc = lib().rf_physkeys_value_material(self._h, node, None, 0, ctypes.byref(ln))
+        if rc != RF_OK and ln.value == 0:
+            _check(rc)
+        out = np.zeros(max(ln.value, 1), dtype=np.uint8)
+        _check(lib().rf_physkeys_value_material(self._h, node, _ptr(out), ln.value, ctypes.byref(ln)))
+        return out[:ln.value].tobytes()
+
+    def stats(self) -> PhysKeysStats:
+        st = PhysKeysStats()
+        _check(lib().rf_physkeys_stats_get(self._h, ctypes.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().rf_physkeys_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def physkeys_flat(dep_ptr, deps, phys_row, suffixes, nodes, n_rows, structure=None, sets=None, keys=None):
+    """rf_physkeys_flat (host only): values as the dict of FilesetForest.copy()
+    (structure) or as fileset objects (sets), value d belonging to nodes[d].
+    Returns (keys [n_rows, 32] uint8 -- `keys` filled in where given --, the
+    values' materials as a list of bytes)."""
+    n, dp, de, pr, sp, sb = _phys_graph_args(dep_ptr, deps, phys_row, suffixes)
+    nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+    nv = len(nd)
+    fa, tree, roots, keep = None, None, None, None
+    if structure is not None:
+        o = structure
+        assert len(o["doc_node_ptr"]) == nv + 1
+        fa = ForestArrays(nv, _ptr(o["doc_node_ptr"]), _ptr(o["node_depth"]) if len(o["node_depth"]) else None,
+                          _ptr(o["entry_ptr"]), _ptr(o["path_off"]), _ptr(o["paths"]) if len(o["paths"]) else None,
+                          _ptr(o["ids32"]) if len(o["ids32"]) else None)
+    elif nv:
+        keep = FilesetTreeBuilder()
+        roots = np.array([keep.add(fs) for fs in sets], dtype=np.uint32)
+        tree = keep.struct()
+    k = np.zeros((max(n_rows, 1), 32), dtype=np.uint8) if keys is None else keys
+    offs = np.zeros(nv + 1, dtype=np.uint64)
+    need = ctypes.c_uint64(0)
+
+    def call(out, cap):
+        return lib().rf_physkeys_flat(n, _ptr(dp) if n else None, _ptr(de) if len(de) else None,
+                                      _ptr(pr) if n else None, _ptr(sp) if n else None, _ptr(sb),
+                                      _ptr(nd) if nv else None, nv, ctypes.byref(fa) if fa is not None else None,
+                                      ctypes.byref(tree) if tree is not None else None,
+                                      _ptr(roots) if roots is not None and nv else None, _ptr(k), n_rows, out, cap,
+                                      _ptr(offs), ctypes.byref(need))
+    rc = call(None, 0)
+    if rc != RF_OK and need.value == 0:
+        _check(rc)
+    out = np.zeros(max(need.value, 1), dtype=np.uint8)
+    _check(call(_ptr(out), need.value))
+    return k[:n_rows], [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(nv)]

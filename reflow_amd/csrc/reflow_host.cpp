@@ -1804,4 +1804,102 @@ rf_repo_stats RepoIndex::Stats() {
     return st;
 }
 
+// ---- physical keys on the device ------------------------------------------------
+PhysicalKeys::PhysicalKeys(Engine& e, const std::vector<uint64_t>& dep_ptr, const std::vector<uint32_t>& deps,
+                           const std::vector<uint64_t>& phys_row, const std::vector<std::string>& suffixes)
+    : e_(e), n_(phys_row.size()) {
+    if (dep_ptr.size() != n_ + 1 || suffixes.size() != n_) reflow::Check(RF_EINVAL);
+    std::vector<uint64_t> suffix_ptr{0};
+    std::string blob;
+    for (const std::string& s : suffixes) {
+        blob += s;
+        suffix_ptr.push_back(blob.size());
+    }
+    reflow::Check(rf_physkeys_open(e.ctx(), n_, dep_ptr.data(), deps.data(), phys_row.data(), suffix_ptr.data(),
+                                   reinterpret_cast<const uint8_t*>(blob.data()), &pk_));
+}
+
+PhysicalKeys::~PhysicalKeys() { rf_physkeys_close(pk_); }
+
+void PhysicalKeys::SetValues(const std::vector<uint32_t>& nodes, const rf_fileset_forest* forest) {
+    uint64_t n_docs = 0;
+    reflow::Check(rf_fileset_forest_info(forest, &n_docs, nullptr, nullptr, nullptr, nullptr));
+    if (n_docs != nodes.size()) reflow::Check(RF_EINVAL);
+    reflow::Check(rf_physkeys_set_values_forest(pk_, nodes.data(), forest, nullptr));
+}
+
+void PhysicalKeys::SetValues(const std::vector<uint32_t>& nodes, const std::vector<const Fileset*>& vals) {
+    if (nodes.size() != vals.size()) reflow::Check(RF_EINVAL);
+    TreeArrays a;
+    std::vector<uint32_t> roots;
+    for (const Fileset* f : vals) roots.push_back(a.add(*f));
+    const rf_fileset_tree t = a.tree();
+    reflow::Check(rf_physkeys_set_values_tree(pk_, nodes.data(), &t, roots.data(), roots.size(), nullptr, nullptr));
+}
+
+void PhysicalKeys::ClearValues(const std::vector<uint32_t>& nodes) {
+    reflow::Check(rf_physkeys_clear_values(pk_, nodes.data(), nodes.size()));
+}
+
+PhysicalKeys::Result PhysicalKeys::Update(const std::vector<uint32_t>& nodes, uint32_t flags, void* d_keys32,
+                                          uint64_t n_rows) {
+    Result r;
+    r.nodes.resize(n_);
+    r.computable.resize(n_);
+    rf_physkeys_out o{};
+    o.size = sizeof o;
+    o.cap = n_;
+    o.nodes = r.nodes.data();
+    o.computable = r.computable.data();
+    reflow::Check(rf_physkeys_update(pk_, nodes.data(), nodes.size(), flags, d_keys32, n_rows, &o, nullptr));
+    r.affected = o.affected;
+    r.written = o.keys_written;
+    r.zeroed = o.keys_zeroed;
+    r.material_bytes = o.material_bytes;
+    r.nodes.resize(o.affected);
+    r.computable.resize(o.affected);
+    return r;
+}
+
+namespace {
+struct DeviceRows {
+    rf_ctx* ctx;
+    void* p = nullptr;
+    DeviceRows(rf_ctx* c, uint64_t bytes) : ctx(c) { reflow::Check(rf_malloc(c, bytes ? bytes : 32, &p)); }
+    ~DeviceRows() { (void)rf_free(ctx, p); }
+};
+}  // namespace
+
+PhysicalKeys::Result PhysicalKeys::Update(const std::vector<uint32_t>& nodes, uint32_t flags,
+                                          std::vector<Digest>& keys) {
+    DeviceRows d(e_.ctx(), 32 * keys.size());
+    if (!keys.empty()) reflow::Check(rf_memcpy_h2d(e_.ctx(), d.p, keys[0].b.data(), 32 * keys.size()));
+    Result r = Update(nodes, flags, d.p, keys.size());
+    if (!keys.empty()) reflow::Check(rf_memcpy_d2h(e_.ctx(), keys[0].b.data(), d.p, 32 * keys.size()));
+    return r;
+}
+
+std::vector<Digest> PhysicalKeys::ValueDigests(const std::vector<uint32_t>& nodes) {
+    std::vector<Digest> out(nodes.size());
+    if (nodes.empty()) return out;
+    DeviceRows d(e_.ctx(), 32 * nodes.size());
+    reflow::Check(rf_physkeys_value_digests_device(pk_, nodes.data(), nodes.size(), d.p, nullptr));
+    reflow::Check(rf_memcpy_d2h(e_.ctx(), out[0].b.data(), d.p, 32 * nodes.size()));
+    return out;
+}
+
+std::string PhysicalKeys::ValueMaterial(uint32_t node) {
+    uint64_t len = 0;
+    if (rf_physkeys_value_material(pk_, node, nullptr, 0, &len) != RF_OK && len == 0) reflow::Check(RF_EINVAL);
+    std::string out(len, '\0');
+    reflow::Check(rf_physkeys_value_material(pk_, node, reinterpret_cast<uint8_t*>(out.data()), len, &len));
+    return out;
+}
+
+rf_physkeys_stats PhysicalKeys::Stats() {
+    rf_physkeys_stats st;
+    reflow::Check(rf_physkeys_stats_get(pk_, &st));
+    return st;
+}
+
 }  // namespace reflow

@@ -186,6 +186,18 @@ int empty_forest(rf_fileset_forest** out) {
 
 }  // namespace
 
+bool rf::forest_dev_arrays(const rf_fileset_forest* f, ForestArraysDev* out) {
+    const auto* d = static_cast<const ForestDev*>(f->dev);
+    if (!d) return false;
+    out->ctx = d->ctx;
+    out->node_depth = d->node_depth.as<uint32_t>();
+    out->entry_ptr = d->entry_ptr.as<uint64_t>();
+    out->path_off = d->path_off.as<uint64_t>();
+    out->paths = d->paths.as<uint8_t>();
+    out->ids32 = d->ids.as<uint8_t>();
+    return true;
+}
+
 extern "C" void rf_fileset_forest_free(rf_fileset_forest* f) {
     if (!f) return;
     if (f->dev) f->dev_free(f->dev);

@@ -52,4 +52,15 @@ hipError_t launch_unmarshal_check(const UnDev& u, hipStream_t s);
 // nodes, entries, paths, IDs and sizes of the accepted documents, dense
 hipError_t launch_unmarshal_scatter(const UnDev& u, hipStream_t s);
 
+// unmarshal_dev.cpp: the structure a device-form forest keeps in HBM (valid
+// until rf_fileset_forest_free), for the physical keys (physkeys_dev.cpp).
+// False for a host-form forest.
+struct ForestArraysDev {
+    rf_ctx* ctx = nullptr;
+    const uint32_t* node_depth = nullptr;
+    const uint64_t *entry_ptr = nullptr, *path_off = nullptr;
+    const uint8_t *paths = nullptr, *ids32 = nullptr;
+};
+bool forest_dev_arrays(const rf_fileset_forest* f, ForestArraysDev* out);
+
 }  // namespace rf
